@@ -5,7 +5,25 @@ n = 2048, qTESLA-p-III (q = 856145921), batch = 2^20 polynomials per GPU
 
     python bench.py [--gpus N] [--steps K] [--warmup W]          # config 3
     python bench.py --config {1,2,3,4,5} ...                      # BASELINE configs
+    python bench.py --full ...                                    # + every leg beside the line
+    python bench.py --dump-outputs DIR ...                        # + the last step's outputs
     torchrun --nproc-per-node N bench.py --gpus N ...             # one rank per GPU
+
+A plain run sets up, warms up, times --steps steps and prints the line: the
+rate, ms_per_step and the HIP-event roofline of the timed launches themselves.
+--full adds the legs that take runs of their own (below: the checker legs,
+the CPU baselines, the memory-only pattern floor, the small-batch latency
+legs); --no-check / --no-cpu-baseline / --no-floor drop single legs from a
+--full run and are implied without it.
+
+--dump-outputs DIR: after the timed region rank 0 writes what the last timed
+step left its caller as DIR/<name>.npy (float64, exact for u32), a fixed
+seeded sample of at most 16 MiB of rows per array and the sampled row numbers
+as rows.npy: `x` (the buffer transformed in place) or `z` (a product).  A
+fwd+inv step overwrites its forward half, so `x_fwd` is that half replayed
+once more on the buffer after the region (the step's own input when the
+round trip holds).  The inputs depend only on the arguments, so two builds
+can be compared array for array.
 
 --gpus N > 1 without a launcher (no WORLD_SIZE in the environment): the
 process starts N fresh child ranks itself before it touches the GPU
@@ -36,8 +54,8 @@ launch (8 B per coefficient for a transform, 12 B for a product) / that
 duration.  traffic = measured HBM bytes per launch from
 profiles/pmc_summary.json, only when it was taken on this library build.
 
-After the timed region, outside it (the checker legs, like cpu_baseline):
-the transform round trip over the whole batch on device, and >= 64 sampled
+With --full, after the timed region, outside it (the checker legs, like
+cpu_baseline): the transform round trip over the whole batch on device, and >= 64 sampled
 polynomials of one more launch on the regenerated input compared with the
 CPU oracle (oracle/, test infrastructure; never the measured path).
 cpu_baseline: the oracle's restatement of the reference's serial CPU path
@@ -62,6 +80,7 @@ SIMDS_PER_CU = 4
 VALU_BOUND = {"polymul", "polymul_ntt", "nussbaumer"}
 METRIC = "NTTs/sec (fwd+inv, n=2048 qTESLA-p-III) at batch=2^20; achieved HBM GB/s"
 SEED = 0x5EED0003
+DUMP_ARRAY_BYTES = 16 << 20  # --dump-outputs: float64 bytes per array (at most two arrays + rows.npy)
 PMC_PATH = os.path.join(ROOT, "profiles", "pmc_summary.json")
 # tools-only diagnostic library (ntt-gpu-qtesla_amd/tools/ntt_diag.hip, `make tools`):
 # the transforms' memory-only variants for roofline.pattern_floor_ms
@@ -364,6 +383,28 @@ def pattern_floor(args, ntt_amd, torch, x, stream, steps: int):
             "timing": "region events / steps, after the timed region"}
 
 
+def dump_rows(count: int, n: int):
+    """--dump-outputs: the polynomials of a [count, n] output that are
+    written, the same for every run of the same shape (all of them when they
+    fit DUMP_ARRAY_BYTES as float64, else the first, the last and a seeded draw)."""
+    import numpy as np
+    k = max(2, DUMP_ARRAY_BYTES // (8 * n))
+    if count <= k:
+        return np.arange(count)
+    rng = np.random.default_rng(SEED)
+    return np.unique(np.concatenate([[0, count - 1], 1 + rng.choice(count - 2, k - 2, replace=False)]))
+
+
+def dump_outputs(out_dir: str, rows, arrays: dict) -> list[str]:
+    """Write rows.npy and every [len(rows), n] uint32 array as float64 .npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.reshape(len(rows), -1).astype(np.float64))
+    return ["rows"] + list(arrays)
+
+
 def workload_name(op, param, n, q, ring):
     base = {"fwdinv": "fwd+inv negacyclic NTT", "fwd": "forward negacyclic NTT", "inv": "inverse negacyclic NTT",
             "polymul": "fused negacyclic poly-mul",
@@ -392,11 +433,18 @@ def main():
     ap.add_argument("--pageable", action="store_true", help="*_host ops: pageable instead of pinned host buffers")
     ap.add_argument("--chunk", type=int, default=0, help="*_host ops: polys per chunk (0 = library default)")
     ap.add_argument("--slots", type=int, default=0, help="*_host ops: buffer slots (0 = library default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the line: checker legs, CPU baselines, pattern floor, "
+                         "small-batch latency legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (a fixed sample of rows) as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--no-floor", action="store_true", help="skip roofline.pattern_floor_ms (transforms)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_check = args.no_floor = True
     c_op, c_param, c_batch, c_ring = CONFIGS[args.config]
     args.op = args.op or c_op
     args.param = args.param or c_param
@@ -502,6 +550,20 @@ def main():
     alg_bytes = count * n * bytes_per_coeff
     achieved = alg_bytes / (per_kind[dom] * 1e-3) / 1e9
 
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        rows = dump_rows(count, n)
+        trows = torch.as_tensor(rows, device=device)
+
+        def sample(t):
+            return ntt_amd.to_numpy_u32(t.view(count, n)[trows])
+        arrays = {"x": sample(x)} if z is None else {"z": sample(z)}
+        if args.op == "fwdinv":
+            launch("fwd")
+            arrays["x_fwd"] = sample(x)
+            launch("inv")
+        dumped = dump_outputs(args.dump_outputs, rows, arrays)
+
     check = {"roundtrip_identity_full_batch": None, "sampled_vs_oracle": None}
     if not args.no_check:
         check = checker_legs(args, ntt_amd, torch, x, y, z, first, count, n)
@@ -521,7 +583,7 @@ def main():
     if expiries is not None:
         check["slot_sync_expiries"] = expiries
     latency = None
-    if runs_latency_kernels(ntt_amd, args.op, args.param, count) and n <= 2048:
+    if args.full and runs_latency_kernels(ntt_amd, args.op, args.param, count) and n <= 2048:
         try:   # beside the line, like the floor: never part of `value`
             latency = graph_replay(torch, launch, kinds, max(args.steps, 50), device)
         except Exception as e:   # noqa: BLE001
@@ -587,6 +649,7 @@ def main():
         "transforms_per_s": 2 * value if args.op == "fwdinv" else None,
         "roofline": roofline,
         "check": check,
+        "dumped_outputs": dumped,
         "build": {"hash": build_hash},
         "cpu_baseline": None,
     }
@@ -782,6 +845,10 @@ def bench_host(args, ntt_amd, torch, device, rank, world, dist):
     ok = None
     if not args.no_check:
         ok = bool(np.array_equal(c, a)) if nin == 1 else None
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        rows = dump_rows(count, n)
+        dumped = dump_outputs(args.dump_outputs, rows, {"c": c[rows]})
     ctx.close()
     units = world * count * args.steps
     value = units / elapsed
@@ -800,6 +867,7 @@ def bench_host(args, ntt_amd, torch, device, rank, world, dist):
                    "global_batch": world * count, "parallelism": f"batch-shard x{world}"},
         "pcie_gbs": value * pcie_bytes / 1e9 / world,
         "check": {"roundtrip_identity_full_batch": ok},
+        "dumped_outputs": dumped,
     }
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -217,6 +217,23 @@ def test_switch_table_in_library(ntt):
     assert L.ntt_small_batch_radix(0, 0, 1, None) == ntt.NTT_ERR_NULL
 
 
+def test_dump_rows_fixed_and_bounded(tmp_path):
+    """--dump-outputs: the sampled rows depend on the shape alone, hold the
+    first and the last polynomial, and every array stays within
+    DUMP_ARRAY_BYTES as float64 (u32 values survive float64 exactly)."""
+    import numpy as np
+    for count, n in ((1, 1024), (37, 2048), (1 << 20, 2048), (1 << 18, 8192)):
+        rows = bench.dump_rows(count, n)
+        assert np.array_equal(rows, bench.dump_rows(count, n))
+        assert rows[0] == 0 and rows[-1] == count - 1 and len(set(rows.tolist())) == len(rows)
+        assert len(rows) == min(count, bench.DUMP_ARRAY_BYTES // (8 * n))
+    rows = bench.dump_rows(5, 4)
+    a = np.arange(20, dtype=np.uint32).reshape(5, 4) + np.uint32(0xFFFFFFE0)
+    assert bench.dump_outputs(str(tmp_path / "d"), rows, {"x": a}) == ["rows", "x"]
+    back = np.load(tmp_path / "d" / "x.npy")
+    assert back.dtype == np.float64 and np.array_equal(back.astype(np.uint32), a)
+
+
 def test_native_latency_reports_instead_of_raising():
     """The config-1 line's native per-call leg (ntt_main -speedgpu 12 as a
     child process) is a diagnostic: without a GPU (here) it reports why, it

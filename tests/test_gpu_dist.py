@@ -42,7 +42,7 @@ def test_shards_concatenate_to_single_process_result(ntt, tmp_path):
 def test_bench_two_ranks_counts_both(ntt):
     batch, steps = 8192, 3
     r = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", str(batch), "--steps", str(steps),
-                   "--warmup", "1", "--dist-backend", "gloo", "--no-cpu-baseline",
+                   "--warmup", "1", "--dist-backend", "gloo", "--full", "--no-cpu-baseline",
                    "--allow-shared-devices"])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -75,7 +75,7 @@ def test_bench_two_ranks_rccl(ntt):
     if torch.cuda.device_count() < 2:
         pytest.skip("RCCL needs one device per rank; this box has one GPU")
     r = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "4096", "--steps", "2",
-                   "--warmup", "1", "--dist-backend", "nccl", "--no-cpu-baseline"])
+                   "--warmup", "1", "--dist-backend", "nccl", "--full", "--no-cpu-baseline"])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert d["config"]["dist_backend"] == "nccl" and d["check"]["all_ranks_ok"] is True
@@ -93,7 +93,7 @@ def test_bench_spawns_ranks_without_launcher(ntt):
     itself and the line counts both ranks' polynomials."""
     batch, steps = 4096, 3
     r = _bench(["--gpus", "2", "--allow-shared-devices", "--batch", str(batch), "--steps", str(steps),
-                "--warmup", "1", "--no-cpu-baseline"])
+                "--warmup", "1", "--full", "--no-cpu-baseline"])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -122,7 +122,7 @@ def test_bench_two_ranks_product_configs(ntt, config):
     global_batch accounting, with the VALU roofline block of a product line."""
     batch, steps = 4096, 2
     r = _bench(["--config", str(config), "--gpus", "2", "--allow-shared-devices", "--batch", str(batch),
-                "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline"])
+                "--steps", str(steps), "--warmup", "1", "--full", "--no-cpu-baseline"])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout

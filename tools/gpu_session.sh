@@ -35,10 +35,10 @@ for step in "${steps[@]}"; do
         smoke)  run smoke 240 python -c "import __graft_entry__ as g; g.smoke()" ;;
         pytest) run pytest 600 python -u -m pytest tests -x -q -m gpu --timeout 120 --timeout-method thread ;;
         pytestq) run pytest 600 python -m pytest tests -x -q -m "gpu and not slow" ;;
-        bench)  run bench 400 python bench.py --steps 10 --warmup 2 --cpu-seconds 8 ;;
-        benchq) run bench 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline ;;
-        benchmul) run benchmul 300 python bench.py --op polymul --steps 10 --warmup 2 --no-cpu-baseline ;;
-        bench1k) run bench1k 300 python bench.py --op fwd --param p-I --batch 65536 --steps 20 --warmup 2 --no-cpu-baseline ;;
+        bench)  run bench 400 python bench.py --full --steps 10 --warmup 2 --cpu-seconds 8 ;;
+        benchq) run bench 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline ;;
+        benchmul) run benchmul 300 python bench.py --full --op polymul --steps 10 --warmup 2 --no-cpu-baseline ;;
+        bench1k) run bench1k 300 python bench.py --full --op fwd --param p-I --batch 65536 --steps 20 --warmup 2 --no-cpu-baseline ;;
         prof)   run prof 400 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline ;;
         variants) run variants 300 python tools/variants.py --rounds 5 ;;
         variants1k) run variants1k 300 python tools/variants.py --param p-I --batch 1048576 --rounds 5 ;;
@@ -64,16 +64,16 @@ for step in "${steps[@]}"; do
                   run pmcb_write 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmcb_write -o run -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-check &&
                   run pmcb_sum 60 python3 tools/pmc_summary.py gpurun_out/pmcb_fetch/run_counter_collection.csv gpurun_out/pmcb_write/run_counter_collection.csv gpurun_out/pmc_summary.json ;;
         profbench) run profbench 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/profbench -o run -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline ;;
-        abmul) for f in ntt-gpu-qtesla_amd/lib/ab/*.so; do b=$(basename $f .so); NTT_AMD_LIB=$PWD/$f run abmul_$b 200 python bench.py --op polymul --steps 5 --warmup 1 --no-cpu-baseline || exit 1; NTT_AMD_LIB=$PWD/$f run abmul1k_$b 200 python bench.py --op polymul --param p-I --steps 5 --warmup 1 --no-cpu-baseline || exit 1; done ;;
+        abmul) for f in ntt-gpu-qtesla_amd/lib/ab/*.so; do b=$(basename $f .so); NTT_AMD_LIB=$PWD/$f run abmul_$b 200 python bench.py --full --op polymul --steps 5 --warmup 1 --no-cpu-baseline || exit 1; NTT_AMD_LIB=$PWD/$f run abmul1k_$b 200 python bench.py --full --op polymul --param p-I --steps 5 --warmup 1 --no-cpu-baseline || exit 1; done ;;
         nustest) run nustest 400 python -m pytest tests/test_gpu_nussbaumer.py -x -q -m "gpu and not slow" ;;
-        nusbench) run nusbench_q 300 python bench.py --op nussbaumer --ring q --steps 5 --warmup 1 --no-cpu-baseline &&
-                  run nusbench_m32 300 python bench.py --op nussbaumer --ring m32 --steps 5 --warmup 1 --no-cpu-baseline &&
-                  run nusbench_q1k 300 python bench.py --op nussbaumer --ring q --param p-I --steps 5 --warmup 1 --no-cpu-baseline ;;
+        nusbench) run nusbench_q 300 python bench.py --full --op nussbaumer --ring q --steps 5 --warmup 1 --no-cpu-baseline &&
+                  run nusbench_m32 300 python bench.py --full --op nussbaumer --ring m32 --steps 5 --warmup 1 --no-cpu-baseline &&
+                  run nusbench_q1k 300 python bench.py --full --op nussbaumer --ring q --param p-I --steps 5 --warmup 1 --no-cpu-baseline ;;
         # config 2's launch is ~0.11 ms: 1000 steps (0.1 s) so that the region
         # events time a steady stream of launches, not the clock ramp after idle
         # (20 / 200 / 1000 steps: 0.116 / 0.119 / 0.111 ms, profiles/r03/c2/steps.log)
         # config 1 (one polynomial per call, ~5-8 us of Python submission each) likewise
-        bench_c*) c=${step#bench_c}; k=20; [ "$c" = 2 ] || [ "$c" = 1 ] && k=1000; run bench_c$c 500 python bench.py --config $c --steps $k --warmup 3 --cpu-seconds 10 ;;
+        bench_c*) c=${step#bench_c}; k=20; [ "$c" = 2 ] || [ "$c" = 1 ] && k=1000; run bench_c$c 500 python bench.py --full --config $c --steps $k --warmup 3 --cpu-seconds 10 ;;
         # rocprofv3 averages include the warm-up launches (clock ramp): 100 timed
         # steps (config 2: 1000, like its bench line) keep them a small share
         prof_c*) c=${step#prof_c}; k=100; [ "$c" = 2 ] && k=1000; run prof_c$c 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_c$c -o run -- python3 bench.py --config $c --steps $k --warmup 3 --no-cpu-baseline --no-check ;;
@@ -88,11 +88,11 @@ for step in "${steps[@]}"; do
                 run pmcm_${n}_fetch 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmcm_${n}_fetch -o run -- python3 bench.py $a &&
                 run pmcm_${n}_write 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmcm_${n}_write -o run -- python3 bench.py $a &&
                 run pmcm_${n}_sum 60 python3 tools/pmc_summary.py --op polymul --param p-III-$n --batch $b --fetch gpurun_out/pmcm_${n}_fetch/run_counter_collection.csv --write gpurun_out/pmcm_${n}_write/run_counter_collection.csv --out gpurun_out/pmc_summary.json ;;
-        benchm_*) n=${step#benchm_}; b=$((1073741824 / n)); run benchm_$n 300 python bench.py --op polymul --param p-III-$n --batch $b --steps 20 --warmup 3 --cpu-seconds 5 &&
-                  run benchmn_$n 300 python bench.py --op polymul_ntt --param p-III-$n --batch $b --steps 20 --warmup 3 --cpu-seconds 5 ;;
+        benchm_*) n=${step#benchm_}; b=$((1073741824 / n)); run benchm_$n 300 python bench.py --full --op polymul --param p-III-$n --batch $b --steps 20 --warmup 3 --cpu-seconds 5 &&
+                  run benchmn_$n 300 python bench.py --full --op polymul_ntt --param p-III-$n --batch $b --steps 20 --warmup 3 --cpu-seconds 5 ;;
         profm_*) n=${step#profm_}; b=$((1073741824 / n)); run profm_$n 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/profm_$n -o run -- python3 bench.py --op polymul --param p-III-$n --batch $b --steps 100 --warmup 3 --no-cpu-baseline --no-check ;;
         profl_*) n=${step#profl_}; b=$((8589934592 / 4 / n)); run profl_$n 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/profl_$n -o run -- python3 bench.py --op fwdinv --param p-III-$n --batch $b --steps 100 --warmup 3 --no-cpu-baseline --no-check ;;
-        benchl_*) n=${step#benchl_}; b=$((8589934592 / 4 / n)); run benchl_$n 300 python bench.py --op fwdinv --param p-III-$n --batch $b --steps 20 --warmup 3 --cpu-seconds 5 ;;
+        benchl_*) n=${step#benchl_}; b=$((8589934592 / 4 / n)); run benchl_$n 300 python bench.py --full --op fwdinv --param p-III-$n --batch $b --steps 20 --warmup 3 --cpu-seconds 5 ;;
         sq_c*) c=${step#sq_c}; run sq_c$c 120 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE --output-format csv -d gpurun_out/sq_c$c -o run -- python3 bench.py --config $c --steps 2 --warmup 1 --no-cpu-baseline --no-check ;;
         sqb_c*) c=${step#sqb_c}; run sqb_c$c 120 rocprofv3 --pmc SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_SALU SQ_INSTS_SMEM SQ_ACTIVE_INST_MISC SQ_INST_CYCLES_VMEM --output-format csv -d gpurun_out/sqb_c$c -o run -- python3 bench.py --config $c --steps 2 --warmup 1 --no-cpu-baseline --no-check ;;
         listpmc) run listpmc 60 rocprofv3 -L ;;
@@ -112,7 +112,7 @@ for step in "${steps[@]}"; do
                  run pmcmn_${n}_write 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmcmn_${n}_write -o run -- python3 bench.py $a &&
                  run pmcmn_${n}_sum 60 python3 tools/pmc_summary.py --op polymul_ntt --param p-III-$n --batch $b --fetch gpurun_out/pmcmn_${n}_fetch/run_counter_collection.csv --write gpurun_out/pmcmn_${n}_write/run_counter_collection.csv --out gpurun_out/pmc_summary.json ;;
         valumn_*) n=${step#valumn_}; b=$((1073741824 / n)); run valumn_$n 120 rocprofv3 --pmc SQ_INSTS_VALU GRBM_GUI_ACTIVE --output-format csv -d gpurun_out/valumn_$n -o run -- python3 bench.py --op polymul_ntt --param p-III-$n --batch $b --steps 3 --warmup 1 --no-cpu-baseline --no-check ;;
-        benchmnx_*) n=${step#benchmnx_}; b=$((1073741824 / n)); run benchmn_$n 300 python bench.py --op polymul_ntt --param p-III-$n --batch $b --steps 20 --warmup 3 --cpu-seconds 5 ;;
+        benchmnx_*) n=${step#benchmnx_}; b=$((1073741824 / n)); run benchmn_$n 300 python bench.py --full --op polymul_ntt --param p-III-$n --batch $b --steps 20 --warmup 3 --cpu-seconds 5 ;;
         valu_c*) c=${step#valu_c}; run valu_c$c 120 rocprofv3 --pmc SQ_INSTS_VALU GRBM_GUI_ACTIVE --output-format csv -d gpurun_out/valu_c$c -o run -- python3 bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline --no-check ;;
         # round 6: the small-batch switch per (n, op): latency vs batch kernels
         # from 64 polynomials to the BASELINE batches (tools/switch_sweep.py)
@@ -156,7 +156,7 @@ for step in "${steps[@]}"; do
               run ab10_4096 300 python tools/ab.py $L --param p-III-4096 --batch 16384 --ops fwd,inv --inplace --rounds 31 &&
               run ab10_8192 300 python tools/ab.py $L --param p-III-8192 --batch 32768 --ops fwd,inv --inplace --rounds 31 ;;
         sweepip) run sweepip 900 python tools/switch_sweep.py ntt-gpu-qtesla_amd/lib/sweep/a_batch.so ntt-gpu-qtesla_amd/lib/sweep/b_lat.so ntt-gpu-qtesla_amd/lib/ab10/r8.so ntt-gpu-qtesla_amd/lib/ab10/r16.so --ops fwd,inv --inplace --rounds 5 --out gpurun_out/switch_sweep_inplace.json ;;
-        benchp1) run benchp1 300 python bench.py --op fwdinv --param p-I --batch 1048576 --steps 20 --warmup 3 --no-cpu-baseline ;;
+        benchp1) run benchp1 300 python bench.py --full --op fwdinv --param p-I --batch 1048576 --steps 20 --warmup 3 --no-cpu-baseline ;;
         floorio) run floorio_p1 300 python tools/latr_floor.py --param p-I &&
                  run floorio_p1oop 300 python tools/latr_floor.py --param p-I --oop &&
                  run floorio_p3 300 python tools/latr_floor.py --param p-III &&
