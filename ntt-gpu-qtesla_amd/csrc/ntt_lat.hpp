@@ -60,7 +60,8 @@ namespace qntt {
 // 1.600, profiles/r06/latr/floorio_*.log; the in-place and out-of-place
 // sweeps, switch_sweep_inplace.json / switch_sweep_latr.json, ran on two
 // boxes), so at n = 1024 the radix-16 kernel takes every in-place batch above
-// its first tier
+// its first tier that it can launch (kAll below: up to 2^26 - 1 polynomials;
+// the path above that is fixed by arithmetic and has not been run)
 enum LatOp { LAT_FWD, LAT_INV, LAT_FWD_BR, LAT_INV_BR, LAT_MUL, LAT_MUL_NTT, LAT_FWD_OOP, LAT_INV_OOP, LAT_NOPS };
 struct LatTier {
     int rb0;
@@ -77,7 +78,14 @@ constexpr LatTier lat_tier(int ps, int op)
                                                                                     : LatTier{2, ~(size_t)0, 2, 0};
 }
 #else
-constexpr size_t kAll = 0x7FFFFFFF;   // every batch the ABI accepts
+// Every batch whose launch fits: these kernels launch grid = batch workgroups
+// of T threads, and HIP takes no launch with grid x block above 32 bits.  At
+// n = 1024 radix-16 has T = 64 (LatRGeo<10, 4>::T), so its largest batch is
+// 2^26 - 1 polynomials (a 256 GiB buffer); above it lat_radix() answers 0 and
+// the batch kernels, whose grid does not grow with the batch, take the call.
+// ntt_latr.hpp asserts max x T <= 2^32 - 1 for every entry of the table.
+constexpr size_t kLaunchMax = 0xFFFFFFFFu;
+constexpr size_t kAll = kLaunchMax / (1024 / 16);
 constexpr LatTier kLatTier[5][LAT_NOPS] = {
     // fwd (in place)         inv (in place)         fwd_br               inv_br                mul              mul_ntt          fwd_oop                inv_oop
     {{2, 1024, 4, kAll}, {2, 1024, 4, kAll}, {2, 1024, 3, 4096}, {2, 1024, 3, 32768}, {2, 2816, 0, 0}, {2, 5120, 0, 0}, {2, 1024, 4, 262144}, {2, 1024, 4, 262144}},  // ref

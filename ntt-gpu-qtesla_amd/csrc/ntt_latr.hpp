@@ -112,6 +112,44 @@ struct LatRGeo {
     static constexpr uint32_t LDS_WORDS = (DB ? 2 : 1) * BUF;
 };
 
+#ifndef NTT_LAT_FORCE
+// Launch size of the small-batch tiers (kLatTier, ntt_lat.hpp): grid = batch
+// workgroups of T threads must stay within 32 bits for every batch a tier
+// takes, for all 5 parameter sets, 8 entry points and both tiers.
+constexpr int lat_threads(int logn, int rb)
+{
+    switch (10 * logn + rb) {
+    case 102: return LatGeo<10>::T;
+    case 103: return LatRGeo<10, 3>::T;
+    case 104: return LatRGeo<10, 4>::T;
+    case 112: return LatGeo<11>::T;
+    case 113: return LatRGeo<11, 3>::T;
+    case 114: return LatRGeo<11, 4>::T;
+    case 122: return LatGeo<12>::T;
+    case 123: return LatRGeo<12, 3>::T;
+    case 124: return LatRGeo<12, 4>::T;
+    case 132: return LatGeo<13>::T;
+    case 133: return LatRGeo<13, 3>::T;
+    case 134: return LatRGeo<13, 4>::T;
+    default: return 0;   // rb = 0: no tier
+    }
+}
+constexpr bool lat_tiers_launchable()
+{
+    constexpr int logn[5] = {PSel<0>::T::LOGN, PSel<1>::T::LOGN, PSel<2>::T::LOGN, PSel<3>::T::LOGN, PSel<4>::T::LOGN};
+    for (int ps = 0; ps < 5; ++ps)
+        for (int op = 0; op < LAT_NOPS; ++op) {
+            const LatTier t = kLatTier[ps][op];
+            const size_t t0 = (size_t)lat_threads(logn[ps], t.rb0), t1 = (size_t)lat_threads(logn[ps], t.rb1);
+            if ((t.max0 && !t0) || (t.max1 && !t1)) return false;   // a tier without a kernel
+            if (t.max0 * t0 > kLaunchMax || t.max1 * t1 > kLaunchMax) return false;
+        }
+    return true;
+}
+static_assert(lat_tiers_launchable(), "a small-batch tier takes a batch whose grid x block exceeds 32 bits");
+static_assert(kAll == kLaunchMax / LatRGeo<10, 4>::T && kAll == (1u << 26) - 1, "kAll: the largest radix-16 launch at n = 1024");
+#endif
+
 // Every pass's twiddles of one direction for thread t: w[j][slot(i, m)] is
 // stage g0(j) + i's twiddle for the e with e >> (i+1) == m.
 template <int PS, bool INV, int RB>

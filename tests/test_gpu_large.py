@@ -37,7 +37,9 @@ def test_large_fwd_inv_random(ntt, oracle, dev, ps, batch):
 
 
 @pytest.mark.parametrize("ps", LARGE_SETS)
-@pytest.mark.parametrize("reps", [1, 100])   # 6 / 600 polynomials: latency kernels / batch kernels
+# (6 / 600 polynomials; which kernel family a batch runs follows the switch table,
+# and test_gpu_family_matrix.py reaches every family of every entry point)
+@pytest.mark.parametrize("reps", [1, 100])
 def test_large_edge_values_and_lazy_inputs(ntt, oracle, dev, ps, reps):
     n, q = ntt.param_info(ps)["n"], ntt.param_info(ps)["q"]
     cases = np.stack([np.zeros(n, np.uint32), np.full(n, q - 1, np.uint32),
@@ -60,7 +62,7 @@ def test_large_edge_values_and_lazy_inputs(ntt, oracle, dev, ps, reps):
 
 
 @pytest.mark.parametrize("ps", LARGE_SETS)
-@pytest.mark.parametrize("reps", [1, 600])   # latency kernels / batch kernels
+@pytest.mark.parametrize("reps", [1, 600])   # families per batch: test_gpu_family_matrix.py
 def test_large_out_of_place_and_pattern(ntt, oracle, dev, ps, reps):
     n = ntt.param_info(ps)["n"]
     pat = np.zeros((1, n), np.uint32)

@@ -60,7 +60,9 @@ def test_fwd_inv_random(ntt, oracle, dev, ps, batch):
 
 
 @pytest.mark.parametrize("ps", PARAM_SETS)
-@pytest.mark.parametrize("batch", [1, 3, 130, 2100])   # 2100: past the latency kernels' 2^21 coefficients
+# (which kernel family a batch runs is the switch table's business and moves with it:
+# test_gpu_family_matrix.py reaches every family of every entry point)
+@pytest.mark.parametrize("batch", [1, 3, 130, 2100])
 def test_bitrev_order_transforms(ntt, oracle, dev, ps, batch):
     """poly_ntt_bitrev / poly_invntt_bitrev: the NTT domain in bit-reversed order,
     as the reference's CT-CT pipeline keeps it (bit_reverse_copy_tbl_gpu +
@@ -90,7 +92,7 @@ def test_bitrev_order_transforms(ntt, oracle, dev, ps, batch):
 
 
 @pytest.mark.parametrize("ps", PARAM_SETS)
-@pytest.mark.parametrize("batch", [33, 2100])   # latency kernels / batch kernels
+@pytest.mark.parametrize("batch", [33, 2100])   # families per batch: test_gpu_family_matrix.py
 def test_out_of_place_keeps_input(ntt, oracle, dev, ps, batch):
     x = oracle.fill_uniform(batch, ps, 7, 0)
     tin = _dev(ntt, x, dev)
@@ -104,7 +106,7 @@ def test_out_of_place_keeps_input(ntt, oracle, dev, ps, batch):
 
 
 @pytest.mark.parametrize("ps", PARAM_SETS)
-@pytest.mark.parametrize("batch", [1, 5, 128, 2100])   # 2100: past the latency kernels' 2^21 coefficients
+@pytest.mark.parametrize("batch", [1, 5, 128, 2100])   # families per batch: test_gpu_family_matrix.py
 def test_poly_mul_random(ntt, oracle, dev, ps, batch):
     a = oracle.fill_uniform(batch, ps, 11 + batch, 0)
     b = oracle.fill_uniform(batch, ps, 12 + batch, 0)
@@ -150,7 +152,7 @@ def test_pointwise(ntt, oracle, dev, ps):
 
 
 @pytest.mark.parametrize("ps", PARAM_SETS)
-@pytest.mark.parametrize("reps", [1, 420])   # 5 / 2100 polynomials: latency kernels / batch kernels
+@pytest.mark.parametrize("reps", [1, 420])   # 5 / 2100 polynomials (families per batch: test_gpu_family_matrix.py)
 def test_edge_values(ntt, oracle, dev, ps, reps):
     n, q = ntt.param_info(ps)["n"], ntt.param_info(ps)["q"]
     cases = np.stack([np.zeros(n, np.uint32), np.full(n, q - 1, np.uint32),
@@ -170,7 +172,7 @@ def test_edge_values(ntt, oracle, dev, ps, reps):
 
 
 @pytest.mark.parametrize("ps", PARAM_SETS)
-@pytest.mark.parametrize("batch", [4, 2100])   # latency kernels / batch kernels
+@pytest.mark.parametrize("batch", [4, 2100])   # families per batch: test_gpu_family_matrix.py
 def test_lazy_inputs_below_2q(ntt, oracle, dev, ps, batch):
     """Inputs in [q, 2q) are tolerated: result == transform of (input mod q)."""
     q = ntt.param_info(ps)["q"]
@@ -329,31 +331,13 @@ def test_bitrev_copy(ntt, oracle, dev, ps, batch):
     assert np.array_equal(_u32(ntt, t), want)
 
 
-# switch points above this batch are not tested (an in-place n = 1024
-# transform takes the radix-16 kernels for every batch the ABI accepts)
-MAX_TEST_BATCH = 1 << 20
-
-
-def _switch_points(ntt, ps, op):
-    """Every batch at which entry point `op` changes kernel family
-    (ntt_small_batch_radix: radix-4 / 8 / 16 one-polynomial-per-workgroup
-    tiers, then the batch kernels), found by bisection: the last batch of each
-    tier and the first of the next."""
-    m = ntt.small_batch_max(ps, op)
-    pts = []
-    lo = 1
-    while lo <= m and lo < MAX_TEST_BATCH:
-        r = ntt.small_batch_radix(ps, op, lo)
-        a, b = lo, m + 1          # radix(a) == r, radix(b) != r
-        while b - a > 1:
-            mid = (a + b) // 2
-            if ntt.small_batch_radix(ps, op, mid) == r:
-                a = mid
-            else:
-                b = mid
-        pts += [a, b]
-        lo = b
-    return sorted(p for p in set(pts) if p <= MAX_TEST_BATCH)
+# Switch points above MAX_TEST_BATCH (2^20) are not run: an in-place n = 1024
+# transform stays on the radix-16 kernels up to 2^26 - 1 polynomials, the
+# largest launch that fits (csrc/ntt_lat.hpp), and the batch kernels take the
+# call above it -- a 256 GiB buffer, pinned by arithmetic alone in
+# test_family_cells.py::test_launch_size_limit.  The walk over the library's
+# switch functions is shared with test_gpu_family_matrix.py (family_cells.py).
+from family_cells import MAX_TEST_BATCH, switch_points as _switch_points  # noqa: E402,F401
 
 
 @pytest.mark.parametrize("ps", PARAM_SETS + LARGE_SETS)
