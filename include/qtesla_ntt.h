@@ -135,6 +135,33 @@ int poly_mul(uint32_t *d_c, const uint32_t *d_a, const uint32_t *d_b,
 int poly_mul_ntt(uint32_t *d_c, const uint32_t *d_a, const uint32_t *d_bhat,
                  size_t batch, int param_set, void *stream);
 
+/* Shared NTT-domain rows times a batch, one launch -- qTESLA's
+ * t_i = a_i * y (+ e_i) over its k public polynomials, which it samples
+ * directly in the NTT domain (k = 1 / 4 / 5 for ref / p-I / p-III):
+ *   out[b][i] = a_i * y_b (+ add[b][i])  mod (x^n + 1, q),  0 <= i < k
+ *   d_y    [batch][n]      natural order, entries < 2q
+ *   d_ahat [k][n]          a_i-hat = poly_ntt(a_i), natural order, entries < 2q;
+ *                          shared by the whole batch
+ *   d_add  NULL, or [batch][k][n] entries < 2q (may equal d_out: accumulate in place)
+ *   d_out  [batch][k][n]   canonical, in [0, q)
+ * Each y_b is read and transformed once: k + 1 transforms of work per y_b
+ * where k poly_mul_ntt calls over a materialised broadcast of a_i-hat take
+ * 2k.  n = 1024 / 2048 sets only (NTT_ERR_PARAM otherwise, and for k outside
+ * 1 .. NTT_MUL_K_MAX).  d_out must not overlap d_y or d_ahat, and d_add may
+ * overlap d_out only by being equal to it (NTT_ERR_ALIAS); d_add may overlap
+ * the inputs. */
+#define NTT_MUL_K_MAX 8
+int poly_mul_ntt_k(uint32_t *d_out, const uint32_t *d_y, const uint32_t *d_ahat,
+                   const uint32_t *d_add, size_t batch, int k, int param_set, void *stream);
+/* Launch shape of poly_mul_ntt_k (either out pointer may be NULL).
+ * *split_max_batch: the largest batch at which the k rows of each polynomial
+ * are spread over k workgroups (each recomputes the forward transform of
+ * y_b; 0 = never); larger batches run one work unit per y_b.  Both give
+ * identical results; the threshold is the measured crossover of their launch
+ * times.  *waves_per_workgroup: work units (one n = 2048 polynomial, or two
+ * n = 1024 polynomials) a workgroup processes side by side. */
+int ntt_mul_k_shape(int param_set, size_t *split_max_batch, int *waves_per_workgroup);
+
 /* Nussbaumer negacyclic product (the paper's alternate algorithm): the
  * reference's single-polynomial CPU routine nussbaumer_fft (NTT.cu:167-277,
  * driver test_nussbaumer :1987-2005), batched on the GPU and extended from

@@ -18,6 +18,7 @@
 #include "ntt_eo.hpp"
 #include "ntt_lat.hpp"
 #include "ntt_latr.hpp"
+#include "ntt_mulk.hpp"
 #include "ntt_internal.h"
 #include "params.hpp"
 #include "pset.hpp"
@@ -101,14 +102,14 @@ struct Launch {
     uint32_t grid, ppw;
 };
 enum Op { OP_XFORM, OP_MUL };
-Launch launch_for(Op op, int ps, size_t npoly, const DevInfo &d, int wg = 0)
+Launch launch_for(Op op, int ps, size_t npoly, const DevInfo &d, int wg = 0, size_t ppw_max = NTT_PPW_MAX)
 {
     const size_t upw = param_set(ps)->logn == 11 ? 1 : 2;
     const size_t units = (npoly + upw - 1) / upw;
     const size_t waves = (size_t)(wg ? wg : op == OP_MUL ? MUL_WG : NTT_WG) / 64;
     const size_t min_groups = (size_t)d.cus * NTT_MIN_WG_PER_CU;
     size_t ppw = units / (waves * min_groups);
-    ppw = ppw < 1 ? 1 : (ppw > NTT_PPW_MAX ? NTT_PPW_MAX : ppw);
+    ppw = ppw < 1 ? 1 : (ppw > ppw_max ? ppw_max : ppw);
     Launch l;
     l.grid = (uint32_t)((units + waves * ppw - 1) / (waves * ppw));
     l.ppw = (uint32_t)ppw;
@@ -166,6 +167,7 @@ enum Xform { FWD, INV, FWD_BR, INV_BR, BITREV };
 static_assert((int)FWD == (int)LAT_FWD && (int)INV == (int)LAT_INV && (int)FWD_BR == (int)LAT_FWD_BR &&
                   (int)INV_BR == (int)LAT_INV_BR,
               "switch table order");
+static_assert(MULK_K_MAX == NTT_MUL_K_MAX, "ABI row limit");
 static_assert(LAT_FWD == NTT_OP_FWD && LAT_INV == NTT_OP_INV && LAT_FWD_BR == NTT_OP_FWD_BR &&
                   LAT_INV_BR == NTT_OP_INV_BR && LAT_MUL == NTT_OP_MUL && LAT_MUL_NTT == NTT_OP_MUL_NTT &&
                   LAT_FWD_OOP == NTT_OP_FWD_OOP && LAT_INV_OOP == NTT_OP_INV_OOP,
@@ -310,6 +312,30 @@ template <int PS> struct LPw {
     }
 };
 
+// poly_mul_ntt_k (ntt_mulk.hpp): the batch kernels' launch shape; up to the
+// measured switch batch the rows are spread over gridDim.y
+template <int PS> struct LMulK {
+    static int run(const uint32_t *y, const uint32_t *ahat, const uint32_t *add, uint32_t *out, size_t batch, int k,
+                   hipStream_t s, const DevInfo &d)
+    {
+        if constexpr (PS < LARGE_PS0) {
+            const Launch l = launch_for(OP_MUL, PS, batch, d, MULK_WG, MULK_PPW_MAX);
+            const dim3 g(l.grid, batch <= mulk_split_max(PS) ? (uint32_t)k : 1u), blk(MULK_WG);
+            if (add) hipLaunchKernelGGL((k_poly_mul_k<PS, true>), g, blk, 0, s, y, ahat, add, out, (uint32_t)batch, (uint32_t)k, l.ppw);
+            else hipLaunchKernelGGL((k_poly_mul_k<PS, false>), g, blk, 0, s, y, ahat, add, out, (uint32_t)batch, (uint32_t)k, l.ppw);
+            return finish_launch();
+        } else {
+            return NTT_ERR_PARAM;
+        }
+    }
+};
+
+bool ranges_overlap(const void *x, size_t xbytes, const void *y, size_t ybytes)
+{
+    const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
+    return a < b + ybytes && b < a + xbytes;
+}
+
 int transform(Xform k, uint32_t *out, const uint32_t *in, size_t batch, int ps, void *stream)
 {
     int rc = check_common(ps, in, batch);
@@ -422,6 +448,35 @@ int poly_mul(uint32_t *d_c, const uint32_t *d_a, const uint32_t *d_b, size_t bat
 int poly_mul_ntt(uint32_t *d_c, const uint32_t *d_a, const uint32_t *d_bhat, size_t batch, int ps, void *stream)
 {
     return mul_common(d_c, d_a, d_bhat, batch, ps, stream, true);
+}
+
+int poly_mul_ntt_k(uint32_t *d_out, const uint32_t *d_y, const uint32_t *d_ahat, const uint32_t *d_add, size_t batch,
+                   int k, int ps, void *stream)
+{
+    const ParamSet *p = param_set(ps);
+    if (!p || p->n > 2048) return NTT_ERR_PARAM;   // n = 1024 / 2048, the sets qTESLA defines
+    if (k < 1 || k > NTT_MUL_K_MAX) return NTT_ERR_PARAM;
+    if (batch == 0) return NTT_OK;
+    if (!d_out || !d_y || !d_ahat) return NTT_ERR_NULL;
+    if ((((uintptr_t)d_out) | ((uintptr_t)d_y) | ((uintptr_t)d_ahat) | ((uintptr_t)d_add)) & 3u) return NTT_ERR_ALIGN;
+    if (batch > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
+    const size_t row = (size_t)p->n * 4, obytes = batch * k * row;
+    if (ranges_overlap(d_out, obytes, d_y, batch * row) || ranges_overlap(d_out, obytes, d_ahat, k * row))
+        return NTT_ERR_ALIAS;
+    if (d_add && partial_overlap(d_add, d_out, obytes)) return NTT_ERR_ALIAS;
+    int rc;
+    DevInfo *d = nullptr;
+    if ((rc = device_ready(&d)) != NTT_OK) return rc;
+    return dispatch<LMulK>(ps, d_y, d_ahat, d_add, d_out, batch, k, (hipStream_t)stream, *d);
+}
+
+int ntt_mul_k_shape(int ps, size_t *split_max_batch, int *waves_per_workgroup)
+{
+    const ParamSet *p = param_set(ps);
+    if (!p || p->n > 2048) return NTT_ERR_PARAM;
+    if (split_max_batch) *split_max_batch = mulk_split_max(ps);
+    if (waves_per_workgroup) *waves_per_workgroup = MULK_WAVES;
+    return NTT_OK;
 }
 
 int poly_mul_nussbaumer(uint32_t *d_c, const uint32_t *d_a, const uint32_t *d_b, size_t batch, int ps, int ring,

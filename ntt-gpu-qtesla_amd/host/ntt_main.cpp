@@ -21,6 +21,10 @@
 //                 sustains, HIP events around R calls) and (b) synchronised
 //                 after every call (the round trip a caller that consumes the
 //                 result sees)
+//   -speedgpu 13  poly_mul_ntt_k, k shared NTT-domain rows times a batch in one
+//                 launch (qTESLA's t_i = a_i y), against the k poly_mul_ntt
+//                 launches over a materialised broadcast it replaces; -k K rows
+//                 (default: the set's k, 1 / 4 / 5 for ref / p-I / p-III)
 //   -param ref|p-I|p-III|p-III-4096|p-III-8192   parameter set (reference:
 //                 compile-time QTESLA set; the n = 4096 / 8192 sets run every
 //                 option but 11, whose Nussbaumer split is n <= 2048)
@@ -34,6 +38,7 @@
 //   -debug        print the first/last coefficients of z (the DEBUG dump)
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -63,11 +68,11 @@
 
 static void help_message()
 {
-    printf("usage: ntt_main -speedgpu {4,6,7,8,9,10,11,12} [-param ref|p-I|p-III|p-III-4096|p-III-8192] [-batch B] [-reps R] [-r seed] [-pcie] [-debug]\n");
+    printf("usage: ntt_main -speedgpu {4,6,7,8,9,10,11,12,13} [-param ref|p-I|p-III|p-III-4096|p-III-8192] [-batch B] [-reps R] [-k K] [-r seed] [-pcie] [-debug]\n");
 }
 
 struct Opts {
-    int option = 6, ps = NTT_PARAM_REF, reps = 1;
+    int option = 6, ps = NTT_PARAM_REF, reps = 1, k = 0;
     size_t batch = 2;
     bool random = false, pcie = false, debug = false;
     uint64_t seed = 0;
@@ -340,6 +345,120 @@ static int run_latency(const Opts &o)
     return 0;
 }
 
+// -speedgpu 13: out[b][i] = a_i * y_b for k shared NTT-domain rows, (a) one
+// poly_mul_ntt_k launch, (b) the baseline it replaces: k back-to-back
+// poly_mul_ntt launches over a materialised [k][batch][n] broadcast of the
+// rows.  Both timed per rep with HIP events on one stream, alternating.
+// All-ones operands: every row is the KAT z[k] = 2k + 2 - n mod q; -r:
+// random operands, the two paths must agree.  The first and last (up to) 256
+// polynomials are checked.
+static int run_mul_ntt_k(const Opts &o)
+{
+    uint32_t n, q;
+    NTT_CALL(ntt_param_info(o.ps, &n, &q, nullptr, nullptr, nullptr, nullptr));
+    const int k = o.k > 0 ? o.k : o.ps == NTT_PARAM_REF ? 1 : o.ps == NTT_PARAM_P_I ? 4 : 5;
+    const size_t row = (size_t)n * 4, pbytes = o.batch * row;
+    uint32_t *d_y, *d_ahat, *d_out, *d_bc, *d_c;
+    HIP_OK(hipMalloc(&d_y, pbytes));
+    HIP_OK(hipMalloc(&d_ahat, k * row));
+    HIP_OK(hipMalloc(&d_out, k * pbytes));
+    HIP_OK(hipMalloc(&d_bc, k * pbytes));   // baseline operand [k][batch][n]
+    HIP_OK(hipMalloc(&d_c, k * pbytes));    // baseline result  [k][batch][n]
+    hipStream_t s;
+    HIP_OK(hipStreamCreate(&s));
+    // dst[0 .. count) = the n-word row at src, by doubling device copies
+    auto bcast = [&](uint32_t *dst, const uint32_t *src, size_t count) {
+        if (dst != src) HIP_OK(hipMemcpyAsync(dst, src, row, hipMemcpyDeviceToDevice, s));
+        for (size_t have = 1; have < count; have *= 2) {
+            const size_t cnt = have < count - have ? have : count - have;
+            HIP_OK(hipMemcpyAsync(dst + have * n, dst, cnt * row, hipMemcpyDeviceToDevice, s));
+        }
+    };
+    if (o.random) {
+        NTT_CALL(ntt_fill_uniform(d_y, o.batch, o.ps, o.seed, 0, s));
+        NTT_CALL(ntt_fill_uniform(d_ahat, k, o.ps, o.seed ^ 0xFFFF, 0, s));
+    } else {
+        const std::vector<uint32_t> ones(n, 1);
+        HIP_OK(hipMemcpy(d_y, ones.data(), row, hipMemcpyHostToDevice));
+        bcast(d_y, d_y, o.batch);
+        bcast(d_ahat, d_y, k);
+    }
+    NTT_CALL(poly_ntt(d_ahat, nullptr, k, o.ps, s));
+    for (int i = 0; i < k; i++) bcast(d_bc + (size_t)i * o.batch * n, d_ahat + (size_t)i * n, o.batch);
+    auto fused = [&]() { NTT_CALL(poly_mul_ntt_k(d_out, d_y, d_ahat, nullptr, o.batch, k, o.ps, s)); };
+    auto base = [&]() {
+        for (int i = 0; i < k; i++)
+            NTT_CALL(poly_mul_ntt(d_c + (size_t)i * o.batch * n, d_y, d_bc + (size_t)i * o.batch * n, o.batch, o.ps, s));
+    };
+    for (int w = 0; w < 3; w++) { fused(); base(); }
+    HIP_OK(hipStreamSynchronize(s));
+    hipEvent_t e0, e1, e2;
+    HIP_OK(hipEventCreate(&e0));
+    HIP_OK(hipEventCreate(&e1));
+    HIP_OK(hipEventCreate(&e2));
+    // small batches: `inner` launches per timed rep (event resolution)
+    const int inner = o.batch * k * n < (1u << 24) ? 20 : 1;
+    std::vector<double> tf, tb;
+    for (int r = 0; r < o.reps; r++) {
+        HIP_OK(hipEventRecord(e0, s));
+        for (int t = 0; t < inner; t++) fused();
+        HIP_OK(hipEventRecord(e1, s));
+        for (int t = 0; t < inner; t++) base();
+        HIP_OK(hipEventRecord(e2, s));
+        HIP_OK(hipEventSynchronize(e2));
+        float a = 0.f, b = 0.f;
+        HIP_OK(hipEventElapsedTime(&a, e0, e1));
+        HIP_OK(hipEventElapsedTime(&b, e1, e2));
+        tf.push_back(a / inner);
+        tb.push_back(b / inner);
+    }
+    auto stats = [](std::vector<double> v, double *lo, double *hi) {
+        std::sort(v.begin(), v.end());
+        *lo = v.front();
+        *hi = v.back();
+        return v[v.size() / 2];
+    };
+    double flo, fhi, blo, bhi;
+    const double fm = stats(tf, &flo, &fhi), bm = stats(tb, &blo, &bhi);
+    // check the head and the tail of the batch
+    const size_t chk = o.batch < 256 ? o.batch : 256;
+    int ok = 1;
+    std::vector<uint32_t> z(k * (size_t)n), c(n);
+    for (int part = 0; part < 2 && ok; part++) {
+        for (size_t t = 0; t < chk && ok; t++) {
+            const size_t b = part ? o.batch - 1 - t : t;
+            HIP_OK(hipMemcpy(z.data(), d_out + b * k * n, k * row, hipMemcpyDeviceToHost));
+            for (int i = 0; i < k && ok; i++) {
+                if (o.random) {
+                    HIP_OK(hipMemcpy(c.data(), d_c + ((size_t)i * o.batch + b) * n, row, hipMemcpyDeviceToHost));
+                    ok = memcmp(c.data(), z.data() + (size_t)i * n, row) == 0;
+                } else {
+                    for (uint32_t j = 0; j < n; j++)
+                        if (z[(size_t)i * n + j] != (uint32_t)((2ull * j + 2 + q - n) % q)) { ok = 0; break; }
+                }
+            }
+        }
+    }
+    printf("\n========================\npoly_mul_ntt_k GPU. Batch Size is %zu, k = %d\n========================\n", o.batch, k);
+    printf("poly_mul_ntt_k      : median %.4f ms (min %.4f, max %.4f over %d reps) per launch, %.3e products/s\n", fm, flo,
+           fhi, o.reps, (double)o.batch * k / fm * 1e3);
+    printf("%d x poly_mul_ntt    : median %.4f ms (min %.4f, max %.4f), %.3e products/s\n", k, bm, blo, bhi,
+           (double)o.batch * k / bm * 1e3);
+    printf("baseline / fused    : %.3f\n", bm / fm);
+    printf("%s: %s\n", o.random ? "fused == k x poly_mul_ntt" : "all-ones KAT z[k] = 2k+2-n mod q, every row",
+           ok ? "Identical." : "Incorrect result.");
+    HIP_OK(hipEventDestroy(e0));
+    HIP_OK(hipEventDestroy(e1));
+    HIP_OK(hipEventDestroy(e2));
+    HIP_OK(hipStreamDestroy(s));
+    HIP_OK(hipFree(d_y));
+    HIP_OK(hipFree(d_ahat));
+    HIP_OK(hipFree(d_out));
+    HIP_OK(hipFree(d_bc));
+    HIP_OK(hipFree(d_c));
+    return ok ? 0 : 1;
+}
+
 int main(int argc, char **argv)
 {
     Opts o;
@@ -362,6 +481,7 @@ int main(int argc, char **argv)
         }
         else if (a == "-batch") { o.batch = strtoull(next(), nullptr, 10); i += 2; }
         else if (a == "-reps") { o.reps = atoi(next()); i += 2; }
+        else if (a == "-k") { o.k = atoi(next()); i += 2; }
         else if (a == "-r") { o.random = true; o.seed = strtoull(next(), nullptr, 0); i += 2; }
         else if (a == "-pcie") { o.pcie = true; i += 1; }
         else if (a == "-debug") { o.debug = true; i += 1; }
@@ -409,6 +529,7 @@ int main(int argc, char **argv)
         return kat ? 0 : 1;
     }
     case 12: return run_latency(o);
+    case 13: return run_mul_ntt_k(o);
     default: help_message(); return -1;
     }
     return 0;

@@ -84,6 +84,8 @@ def lib():
             getattr(L, nm).argtypes = [_vp, _vp, _sz, ctypes.c_int, _vp]
         for nm in ("poly_mul", "poly_mul_ntt", "poly_pointwise"):
             getattr(L, nm).argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, _vp]
+        L.poly_mul_ntt_k.argtypes = [_vp, _vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
+        L.ntt_mul_k_shape.argtypes = [ctypes.c_int, ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_int)]
         L.poly_mul_nussbaumer.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.ntt_fill_uniform.argtypes = [_vp, _sz, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, _vp]
         L.ntt_last_hip_error.restype = ctypes.c_int
@@ -379,6 +381,46 @@ def poly_mul(c, a, b, param_set, stream=None):
 def poly_mul_ntt(c, a, bhat, param_set, stream=None):
     """c = a*b mod (x^n + 1, q) with bhat = poly_ntt(b) given (NTT domain)."""
     return _mul("poly_mul_ntt", c, a, bhat, param_set, stream)
+
+
+MUL_K_MAX = 8   # NTT_MUL_K_MAX
+
+
+def poly_mul_ntt_k(out, y, ahat, param_set, add=None, stream=None):
+    """out[b, i] = a_i * y[b] (+ add[b, i]) mod (x^n + 1, q) for the k rows
+    ahat[i] = poly_ntt(a_i), shared by the whole batch: one launch, y read and
+    transformed once (qTESLA's t_i = a_i y + e_i).
+
+    y is [batch, n], ahat [k, n] with k = ahat.numel() // n, out and add
+    [batch, k, n]; add may be out (accumulate in place)."""
+    n = _n(param_set)
+    k, nb = ahat.numel() // n, y.numel() // n
+    if ahat.numel() != k * n or not 1 <= k <= MUL_K_MAX:
+        raise ValueError(f"ahat: numel {ahat.numel()} is not k*n with 1 <= k <= {MUL_K_MAX} (n={n})")
+    if y.numel() != nb * n:
+        raise ValueError(f"y: numel {y.numel()} is not a multiple of n={n}")
+    if out.numel() != nb * k * n:
+        raise ValueError(f"out: numel {out.numel()} is not batch*k*n = {nb}*{k}*{n}")
+    if add is not None and add.numel() != nb * k * n:
+        raise ValueError(f"add: numel {add.numel()} is not batch*k*n = {nb}*{k}*{n}")
+    tensors = (out, y, ahat) if add is None else (out, y, ahat, add)
+    for t in tensors:
+        _batch(t, n)   # device, dtype, contiguity
+    fn = lib().poly_mul_ntt_k
+    pa = None if add is None else add.data_ptr()
+    _run("poly_mul_ntt_k", tensors, stream,
+         lambda s: fn(out.data_ptr(), y.data_ptr(), ahat.data_ptr(), pa, nb, k, _ps(param_set), s))
+    return out
+
+
+def mul_k_shape(param_set) -> dict:
+    """Launch shape of poly_mul_ntt_k (ntt_mul_k_shape): "split_max", the
+    largest batch whose k rows are spread over k workgroups (0: never), and
+    "waves", the work units (one n = 2048 polynomial or two n = 1024
+    polynomials each) of a workgroup."""
+    v, w = _sz(), ctypes.c_int()
+    _check(lib().ntt_mul_k_shape(_ps(param_set), ctypes.byref(v), ctypes.byref(w)), "ntt_mul_k_shape")
+    return {"split_max": v.value, "waves": w.value}
 
 
 def poly_mul_nussbaumer(c, a, b, param_set, ring="q", stream=None):
