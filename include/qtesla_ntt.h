@@ -162,6 +162,47 @@ int poly_mul_ntt_k(uint32_t *d_out, const uint32_t *d_y, const uint32_t *d_ahat,
  * n = 1024 polynomials) a workgroup processes side by side. */
 int ntt_mul_k_shape(int param_set, size_t *split_max_batch, int *waves_per_workgroup);
 
+/* A k x l matrix of shared NTT-domain polynomials times l batches, summed in
+ * the NTT domain, one launch -- qTESLA's verification w_i = a_i * z - t_i * c
+ * (l = 2: inputs [z, c], row i = [a_i-hat, q - t_i-hat]):
+ *   out[b][i] = sum_{j<l} a_ij * y_j[b]  (+ add[b][i])   mod (x^n + 1, q),  0 <= i < k
+ *   d_y     HOST array of l device pointers, each [batch][n], natural order,
+ *           entries < 2q.  The array is read during the call only; the l
+ *           batches are used where they lie (no interleaving copy)
+ *   d_ahat  [k][l][n]   a_ij-hat = poly_ntt(a_ij), natural order, entries < 2q;
+ *           shared by the whole batch
+ *   d_add   NULL, or [batch][k][n] entries < 2q (may equal d_out: accumulate in place)
+ *   d_out   [batch][k][n] canonical, in [0, q)
+ * There is no subtracting form: a caller that needs - t_i * c stores the
+ * negated row q - t_i-hat (entrywise, 0 stays 0 or becomes q: both < 2q), once
+ * per key.  The NTT is linear, so the l products of a row share one inverse
+ * transform: k + l transforms of work per b where two poly_mul_ntt_k launches
+ * take 2(k + 1), and no addend round trip through memory.  l = 1 is
+ * poly_mul_ntt_k.  n = 1024 / 2048 sets only (NTT_ERR_PARAM otherwise, and
+ * for k outside 1 .. NTT_MUL_K_MAX or l outside 1 .. NTT_MUL_L_MAX).  d_out
+ * must not overlap any d_y[j] or d_ahat (k*l*n words), and d_add may overlap
+ * d_out only by being equal to it (NTT_ERR_ALIAS); the d_y[j] may overlap each
+ * other and d_add freely (d_y[0] == d_y[1] gives (a_i0 + a_i1) * y). */
+#define NTT_MUL_L_MAX 2
+int poly_mul_ntt_kl(uint32_t *d_out, const uint32_t *const *d_y, const uint32_t *d_ahat,
+                    const uint32_t *d_add, size_t batch, int k, int l, int param_set, void *stream);
+/* Launch shape of poly_mul_ntt_kl for l inputs, as ntt_mul_k_shape (l = 1:
+ * exactly that; NTT_ERR_PARAM for l outside 1 .. NTT_MUL_L_MAX). */
+int ntt_mul_kl_shape(int param_set, int l, size_t *split_max_batch, int *waves_per_workgroup);
+
+/* Sparse to dense: out[b][pos[b][j]] = val[b][j] mod q for j < h, every other
+ * coefficient 0 -- qTESLA's challenge c, h positions and signs (+1 -> 1,
+ * -1 -> q - 1) out of the hash, as the dense polynomial every entry point
+ * above takes.
+ *   d_pos, d_val [batch][h] uint32; val < 2q; d_out [batch][n] canonical,
+ *   every word written.
+ * Entries with pos >= n are ignored.  Positions within one polynomial are
+ * distinct (if not, one of the values wins).  1 <= h <= n (NTT_ERR_PARAM
+ * otherwise).  All five parameter sets.  d_out must not overlap d_pos or
+ * d_val (NTT_ERR_ALIAS). */
+int poly_scatter(uint32_t *d_out, const uint32_t *d_pos, const uint32_t *d_val,
+                 size_t batch, int h, int param_set, void *stream);
+
 /* Nussbaumer negacyclic product (the paper's alternate algorithm): the
  * reference's single-polynomial CPU routine nussbaumer_fft (NTT.cu:167-277,
  * driver test_nussbaumer :1987-2005), batched on the GPU and extended from

@@ -19,6 +19,7 @@
 #include "ntt_lat.hpp"
 #include "ntt_latr.hpp"
 #include "ntt_mulk.hpp"
+#include "ntt_mulkl.hpp"
 #include "ntt_internal.h"
 #include "params.hpp"
 #include "pset.hpp"
@@ -168,6 +169,7 @@ static_assert((int)FWD == (int)LAT_FWD && (int)INV == (int)LAT_INV && (int)FWD_B
                   (int)INV_BR == (int)LAT_INV_BR,
               "switch table order");
 static_assert(MULK_K_MAX == NTT_MUL_K_MAX, "ABI row limit");
+static_assert(MULKL_L_MAX == NTT_MUL_L_MAX && NTT_MUL_L_MAX == 2, "ABI column limit (poly_mul_ntt_kl launches l = 2)");
 static_assert(LAT_FWD == NTT_OP_FWD && LAT_INV == NTT_OP_INV && LAT_FWD_BR == NTT_OP_FWD_BR &&
                   LAT_INV_BR == NTT_OP_INV_BR && LAT_MUL == NTT_OP_MUL && LAT_MUL_NTT == NTT_OP_MUL_NTT &&
                   LAT_FWD_OOP == NTT_OP_FWD_OOP && LAT_INV_OOP == NTT_OP_INV_OOP,
@@ -330,6 +332,25 @@ template <int PS> struct LMulK {
     }
 };
 
+// poly_mul_ntt_kl, l = 2 (ntt_mulkl.hpp): poly_mul_ntt_k's launch shape with
+// that kernel's workgroup and its own measured switch batch
+template <int PS> struct LMulKL {
+    static int run(const uint32_t *const *y, const uint32_t *ahat, const uint32_t *add, uint32_t *out, size_t batch, int k,
+                   hipStream_t s, const DevInfo &d)
+    {
+        if constexpr (PS < LARGE_PS0) {
+            const Launch l = launch_for(OP_MUL, PS, batch, d, MULKL_WG, MULKL_PPW_MAX);
+            const dim3 g(l.grid, batch <= mulkl_split_max(PS) ? (uint32_t)k : 1u), blk(MULKL_WG);
+            const MulKLIn<2> in = {{y[0], y[1]}};
+            if (add) hipLaunchKernelGGL((k_poly_mul_kl<PS, 2, true>), g, blk, 0, s, in, ahat, add, out, (uint32_t)batch, (uint32_t)k, l.ppw);
+            else hipLaunchKernelGGL((k_poly_mul_kl<PS, 2, false>), g, blk, 0, s, in, ahat, add, out, (uint32_t)batch, (uint32_t)k, l.ppw);
+            return finish_launch();
+        } else {
+            return NTT_ERR_PARAM;
+        }
+    }
+};
+
 bool ranges_overlap(const void *x, size_t xbytes, const void *y, size_t ybytes)
 {
     const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
@@ -477,6 +498,61 @@ int ntt_mul_k_shape(int ps, size_t *split_max_batch, int *waves_per_workgroup)
     if (split_max_batch) *split_max_batch = mulk_split_max(ps);
     if (waves_per_workgroup) *waves_per_workgroup = MULK_WAVES;
     return NTT_OK;
+}
+
+int poly_mul_ntt_kl(uint32_t *d_out, const uint32_t *const *d_y, const uint32_t *d_ahat, const uint32_t *d_add,
+                    size_t batch, int k, int l, int ps, void *stream)
+{
+    const ParamSet *p = param_set(ps);
+    if (!p || p->n > 2048) return NTT_ERR_PARAM;   // n = 1024 / 2048, the sets qTESLA defines
+    if (k < 1 || k > NTT_MUL_K_MAX || l < 1 || l > NTT_MUL_L_MAX) return NTT_ERR_PARAM;
+    if (batch == 0) return NTT_OK;
+    if (!d_out || !d_y || !d_ahat) return NTT_ERR_NULL;
+    uintptr_t bits = ((uintptr_t)d_out) | ((uintptr_t)d_ahat) | ((uintptr_t)d_add);
+    for (int j = 0; j < l; j++) {
+        if (!d_y[j]) return NTT_ERR_NULL;
+        bits |= (uintptr_t)d_y[j];
+    }
+    if (bits & 3u) return NTT_ERR_ALIGN;
+    if (batch > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
+    const size_t row = (size_t)p->n * 4, obytes = batch * k * row;
+    for (int j = 0; j < l; j++)
+        if (ranges_overlap(d_out, obytes, d_y[j], batch * row)) return NTT_ERR_ALIAS;
+    if (ranges_overlap(d_out, obytes, d_ahat, (size_t)k * l * row)) return NTT_ERR_ALIAS;
+    if (d_add && partial_overlap(d_add, d_out, obytes)) return NTT_ERR_ALIAS;
+    if (l == 1) return poly_mul_ntt_k(d_out, d_y[0], d_ahat, d_add, batch, k, ps, stream);
+    int rc;
+    DevInfo *d = nullptr;
+    if ((rc = device_ready(&d)) != NTT_OK) return rc;
+    return dispatch<LMulKL>(ps, d_y, d_ahat, d_add, d_out, batch, k, (hipStream_t)stream, *d);
+}
+
+int ntt_mul_kl_shape(int ps, int l, size_t *split_max_batch, int *waves_per_workgroup)
+{
+    if (l == 1) return ntt_mul_k_shape(ps, split_max_batch, waves_per_workgroup);
+    const ParamSet *p = param_set(ps);
+    if (!p || p->n > 2048 || l < 1 || l > NTT_MUL_L_MAX) return NTT_ERR_PARAM;
+    if (split_max_batch) *split_max_batch = mulkl_split_max(ps);
+    if (waves_per_workgroup) *waves_per_workgroup = MULKL_WAVES;
+    return NTT_OK;
+}
+
+int poly_scatter(uint32_t *d_out, const uint32_t *d_pos, const uint32_t *d_val, size_t batch, int h, int ps, void *stream)
+{
+    const ParamSet *p = param_set(ps);
+    if (!p || h < 1 || (uint32_t)h > p->n) return NTT_ERR_PARAM;
+    if (batch == 0) return NTT_OK;
+    if (!d_out || !d_pos || !d_val) return NTT_ERR_NULL;
+    if ((((uintptr_t)d_out) | ((uintptr_t)d_pos) | ((uintptr_t)d_val)) & 3u) return NTT_ERR_ALIGN;
+    if (batch > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
+    const size_t obytes = batch * p->n * 4, lbytes = batch * (size_t)h * 4;
+    if (ranges_overlap(d_out, obytes, d_pos, lbytes) || ranges_overlap(d_out, obytes, d_val, lbytes)) return NTT_ERR_ALIAS;
+    int rc;
+    DevInfo *d = nullptr;
+    if ((rc = device_ready(&d)) != NTT_OK) return rc;
+    hipLaunchKernelGGL(k_poly_scatter, dim3((uint32_t)batch), dim3(SCATTER_WG), p->n * 4, (hipStream_t)stream, d_pos, d_val,
+                       d_out, p->n, p->q, (uint32_t)h);
+    return finish_launch();
 }
 
 int poly_mul_nussbaumer(uint32_t *d_c, const uint32_t *d_a, const uint32_t *d_b, size_t batch, int ps, int ring,

@@ -25,6 +25,10 @@
 //                 launch (qTESLA's t_i = a_i y), against the k poly_mul_ntt
 //                 launches over a materialised broadcast it replaces; -k K rows
 //                 (default: the set's k, 1 / 4 / 5 for ref / p-I / p-III)
+//   -speedgpu 14  poly_mul_ntt_kl with l = 2, qTESLA's verification
+//                 w_i = a_i z - t_i c in one launch, against the two
+//                 poly_mul_ntt_k launches it replaces (tmp = (-t_i) c, then
+//                 a_i z + tmp accumulated in place); -k K as for 13
 //   -param ref|p-I|p-III|p-III-4096|p-III-8192   parameter set (reference:
 //                 compile-time QTESLA set; the n = 4096 / 8192 sets run every
 //                 option but 11, whose Nussbaumer split is n <= 2048)
@@ -68,7 +72,7 @@
 
 static void help_message()
 {
-    printf("usage: ntt_main -speedgpu {4,6,7,8,9,10,11,12,13} [-param ref|p-I|p-III|p-III-4096|p-III-8192] [-batch B] [-reps R] [-k K] [-r seed] [-pcie] [-debug]\n");
+    printf("usage: ntt_main -speedgpu {4,6,7,8,9,10,11,12,13,14} [-param ref|p-I|p-III|p-III-4096|p-III-8192] [-batch B] [-reps R] [-k K] [-r seed] [-pcie] [-debug]\n");
 }
 
 struct Opts {
@@ -459,6 +463,133 @@ static int run_mul_ntt_k(const Opts &o)
     return ok ? 0 : 1;
 }
 
+// -speedgpu 14: out[b][i] = a_i * z_b + t'_i * c_b for k rows of two shared
+// NTT-domain polynomials (verification: t'_i-hat = q - t_i-hat), (a) one
+// poly_mul_ntt_kl launch, (b) the composition it replaces: poly_mul_ntt_k of
+// c over the rows t'_i, then poly_mul_ntt_k of z over the rows a_i with the
+// first result as addend, in place.  -speedgpu 13's protocol: both timed per
+// rep with HIP events on one stream, alternating.  All-ones operands: every
+// row is twice the KAT, z[k] = 2 (2k + 2 - n) mod q; -r: random operands, the
+// two paths must agree.  The first and last (up to) 256 polynomials are
+// checked.
+static int run_mul_ntt_kl(const Opts &o)
+{
+    uint32_t n, q;
+    NTT_CALL(ntt_param_info(o.ps, &n, &q, nullptr, nullptr, nullptr, nullptr));
+    const int k = o.k > 0 ? o.k : o.ps == NTT_PARAM_REF ? 1 : o.ps == NTT_PARAM_P_I ? 4 : 5;
+    const size_t row = (size_t)n * 4, pbytes = o.batch * row;
+    uint32_t *d_z, *d_c, *d_a, *d_t, *d_at, *d_out, *d_base;
+    HIP_OK(hipMalloc(&d_z, pbytes));
+    HIP_OK(hipMalloc(&d_c, pbytes));
+    HIP_OK(hipMalloc(&d_a, k * row));        // [k][n]    a_i-hat
+    HIP_OK(hipMalloc(&d_t, k * row));        // [k][n]    t'_i-hat
+    HIP_OK(hipMalloc(&d_at, 2 * k * row));   // [k][2][n] both, the fused launch's rows
+    HIP_OK(hipMalloc(&d_out, k * pbytes));
+    HIP_OK(hipMalloc(&d_base, k * pbytes));
+    hipStream_t s;
+    HIP_OK(hipStreamCreate(&s));
+    // dst[0 .. count) = the n-word row at src, by doubling device copies
+    auto bcast = [&](uint32_t *dst, const uint32_t *src, size_t count) {
+        if (dst != src) HIP_OK(hipMemcpyAsync(dst, src, row, hipMemcpyDeviceToDevice, s));
+        for (size_t have = 1; have < count; have *= 2) {
+            const size_t cnt = have < count - have ? have : count - have;
+            HIP_OK(hipMemcpyAsync(dst + have * n, dst, cnt * row, hipMemcpyDeviceToDevice, s));
+        }
+    };
+    if (o.random) {
+        NTT_CALL(ntt_fill_uniform(d_z, o.batch, o.ps, o.seed, 0, s));
+        NTT_CALL(ntt_fill_uniform(d_c, o.batch, o.ps, o.seed ^ 0xCCCC, 0, s));
+        NTT_CALL(ntt_fill_uniform(d_a, k, o.ps, o.seed ^ 0xFFFF, 0, s));
+        NTT_CALL(ntt_fill_uniform(d_t, k, o.ps, o.seed ^ 0xEEEE, 0, s));
+    } else {
+        const std::vector<uint32_t> ones(n, 1);
+        HIP_OK(hipMemcpy(d_z, ones.data(), row, hipMemcpyHostToDevice));
+        bcast(d_z, d_z, o.batch);
+        bcast(d_c, d_z, o.batch);
+        bcast(d_a, d_z, k);
+        bcast(d_t, d_z, k);
+    }
+    NTT_CALL(poly_ntt(d_a, nullptr, k, o.ps, s));
+    NTT_CALL(poly_ntt(d_t, nullptr, k, o.ps, s));
+    for (int i = 0; i < k; i++) {
+        HIP_OK(hipMemcpyAsync(d_at + (size_t)(2 * i) * n, d_a + (size_t)i * n, row, hipMemcpyDeviceToDevice, s));
+        HIP_OK(hipMemcpyAsync(d_at + (size_t)(2 * i + 1) * n, d_t + (size_t)i * n, row, hipMemcpyDeviceToDevice, s));
+    }
+    const uint32_t *ys[2] = {d_z, d_c};
+    auto fused = [&]() { NTT_CALL(poly_mul_ntt_kl(d_out, ys, d_at, nullptr, o.batch, k, 2, o.ps, s)); };
+    auto base = [&]() {
+        NTT_CALL(poly_mul_ntt_k(d_base, d_c, d_t, nullptr, o.batch, k, o.ps, s));
+        NTT_CALL(poly_mul_ntt_k(d_base, d_z, d_a, d_base, o.batch, k, o.ps, s));
+    };
+    for (int w = 0; w < 3; w++) { fused(); base(); }
+    HIP_OK(hipStreamSynchronize(s));
+    hipEvent_t e0, e1, e2;
+    HIP_OK(hipEventCreate(&e0));
+    HIP_OK(hipEventCreate(&e1));
+    HIP_OK(hipEventCreate(&e2));
+    // small batches: `inner` launches per timed rep (event resolution)
+    const int inner = o.batch * k * n < (1u << 24) ? 20 : 1;
+    std::vector<double> tf, tb;
+    for (int r = 0; r < o.reps; r++) {
+        HIP_OK(hipEventRecord(e0, s));
+        for (int t = 0; t < inner; t++) fused();
+        HIP_OK(hipEventRecord(e1, s));
+        for (int t = 0; t < inner; t++) base();
+        HIP_OK(hipEventRecord(e2, s));
+        HIP_OK(hipEventSynchronize(e2));
+        float a = 0.f, b = 0.f;
+        HIP_OK(hipEventElapsedTime(&a, e0, e1));
+        HIP_OK(hipEventElapsedTime(&b, e1, e2));
+        tf.push_back(a / inner);
+        tb.push_back(b / inner);
+    }
+    auto stats = [](std::vector<double> v, double *lo, double *hi) {
+        std::sort(v.begin(), v.end());
+        *lo = v.front();
+        *hi = v.back();
+        return v[v.size() / 2];
+    };
+    double flo, fhi, blo, bhi;
+    const double fm = stats(tf, &flo, &fhi), bm = stats(tb, &blo, &bhi);
+    // check the head and the tail of the batch
+    const size_t chk = o.batch < 256 ? o.batch : 256;
+    int ok = 1;
+    std::vector<uint32_t> z(k * (size_t)n), c(k * (size_t)n);
+    for (int part = 0; part < 2 && ok; part++) {
+        for (size_t t = 0; t < chk && ok; t++) {
+            const size_t b = part ? o.batch - 1 - t : t;
+            HIP_OK(hipMemcpy(z.data(), d_out + b * k * n, k * row, hipMemcpyDeviceToHost));
+            if (o.random) {
+                HIP_OK(hipMemcpy(c.data(), d_base + b * k * n, k * row, hipMemcpyDeviceToHost));
+                ok = memcmp(c.data(), z.data(), k * row) == 0;
+            } else {
+                for (size_t j = 0; j < (size_t)k * n && ok; j++)
+                    ok = z[j] == (uint32_t)(2 * ((2ull * (j % n) + 2 + q - n) % q) % q);
+            }
+        }
+    }
+    printf("\n========================\npoly_mul_ntt_kl GPU. Batch Size is %zu, k = %d, l = 2\n========================\n", o.batch, k);
+    printf("poly_mul_ntt_kl     : median %.4f ms (min %.4f, max %.4f over %d reps) per launch, %.3e rows/s\n", fm, flo, fhi,
+           o.reps, (double)o.batch * k / fm * 1e3);
+    printf("2 x poly_mul_ntt_k  : median %.4f ms (min %.4f, max %.4f), %.3e rows/s\n", bm, blo, bhi,
+           (double)o.batch * k / bm * 1e3);
+    printf("baseline / fused    : %.3f\n", bm / fm);
+    printf("%s: %s\n", o.random ? "fused == 2 x poly_mul_ntt_k" : "all-ones KAT z[k] = 2 (2k+2-n) mod q, every row",
+           ok ? "Identical." : "Incorrect result.");
+    HIP_OK(hipEventDestroy(e0));
+    HIP_OK(hipEventDestroy(e1));
+    HIP_OK(hipEventDestroy(e2));
+    HIP_OK(hipStreamDestroy(s));
+    HIP_OK(hipFree(d_z));
+    HIP_OK(hipFree(d_c));
+    HIP_OK(hipFree(d_a));
+    HIP_OK(hipFree(d_t));
+    HIP_OK(hipFree(d_at));
+    HIP_OK(hipFree(d_out));
+    HIP_OK(hipFree(d_base));
+    return ok ? 0 : 1;
+}
+
 int main(int argc, char **argv)
 {
     Opts o;
@@ -530,6 +661,7 @@ int main(int argc, char **argv)
     }
     case 12: return run_latency(o);
     case 13: return run_mul_ntt_k(o);
+    case 14: return run_mul_ntt_kl(o);
     default: help_message(); return -1;
     }
     return 0;

@@ -86,6 +86,9 @@ def lib():
             getattr(L, nm).argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, _vp]
         L.poly_mul_ntt_k.argtypes = [_vp, _vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.ntt_mul_k_shape.argtypes = [ctypes.c_int, ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_int)]
+        L.poly_mul_ntt_kl.argtypes = [_vp, ctypes.POINTER(_vp), _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
+        L.ntt_mul_kl_shape.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_int)]
+        L.poly_scatter.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_mul_nussbaumer.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.ntt_fill_uniform.argtypes = [_vp, _sz, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, _vp]
         L.ntt_last_hip_error.restype = ctypes.c_int
@@ -421,6 +424,78 @@ def mul_k_shape(param_set) -> dict:
     v, w = _sz(), ctypes.c_int()
     _check(lib().ntt_mul_k_shape(_ps(param_set), ctypes.byref(v), ctypes.byref(w)), "ntt_mul_k_shape")
     return {"split_max": v.value, "waves": w.value}
+
+
+MUL_L_MAX = 2   # NTT_MUL_L_MAX
+
+
+def poly_mul_ntt_kl(out, ys, ahat, param_set, add=None, stream=None):
+    """out[b, i] = sum_j a_ij * ys[j][b] (+ add[b, i]) mod (x^n + 1, q) for the
+    k x l matrix ahat[i, j] = poly_ntt(a_ij), shared by the whole batch: one
+    launch, the l products of a row summed in the NTT domain (qTESLA's
+    verification w_i = a_i z - t_i c with ys = (z, c), ahat[i] = (a_i-hat,
+    q - t_i-hat)).
+
+    ys is a sequence of l tensors [batch, n] (separate allocations or views,
+    used where they lie), ahat [k, l, n] with k = ahat.numel() // (l * n), out
+    and add [batch, k, n]; add may be out (accumulate in place)."""
+    n = _n(param_set)
+    ys = tuple(ys)
+    l = len(ys)
+    if not 1 <= l <= MUL_L_MAX:
+        raise ValueError(f"ys: {l} tensors, expected 1 .. {MUL_L_MAX}")
+    nb = ys[0].numel() // n
+    for j, y in enumerate(ys):
+        if y.numel() != nb * n:
+            raise ValueError(f"ys: numel of ys[{j}] = {y.numel()} is not batch*n = {nb}*{n}, one batch for all")
+    k = ahat.numel() // (l * n)
+    if ahat.numel() != k * l * n or not 1 <= k <= MUL_K_MAX:
+        raise ValueError(f"ahat: numel {ahat.numel()} is not k*l*n with 1 <= k <= {MUL_K_MAX} (l={l}, n={n})")
+    if out.numel() != nb * k * n:
+        raise ValueError(f"out: numel {out.numel()} is not batch*k*n = {nb}*{k}*{n}")
+    if add is not None and add.numel() != nb * k * n:
+        raise ValueError(f"add: numel {add.numel()} is not batch*k*n = {nb}*{k}*{n}")
+    tensors = (out, *ys, ahat) if add is None else (out, *ys, ahat, add)
+    for t in tensors:
+        _batch(t, n)   # device, dtype, contiguity
+    fn = lib().poly_mul_ntt_kl
+    py = (_vp * l)(*[y.data_ptr() for y in ys])   # host array, read during the call only
+    pa = None if add is None else add.data_ptr()
+    _run("poly_mul_ntt_kl", tensors, stream,
+         lambda s: fn(out.data_ptr(), py, ahat.data_ptr(), pa, nb, k, l, _ps(param_set), s))
+    return out
+
+
+def mul_kl_shape(param_set, l: int) -> dict:
+    """Launch shape of poly_mul_ntt_kl with l inputs (ntt_mul_kl_shape), as
+    mul_k_shape."""
+    v, w = _sz(), ctypes.c_int()
+    _check(lib().ntt_mul_kl_shape(_ps(param_set), l, ctypes.byref(v), ctypes.byref(w)), "ntt_mul_kl_shape")
+    return {"split_max": v.value, "waves": w.value}
+
+
+def poly_scatter(out, pos, val, param_set, stream=None):
+    """out[b, pos[b, j]] = val[b, j] mod q for j < h, every other coefficient 0
+    (qTESLA's challenge c from its h positions and signs).  pos and val are
+    [batch, h] with 1 <= h <= n, val < 2q; out is [batch, n], fully written.
+    Entries with pos >= n are ignored; positions of one polynomial are
+    distinct."""
+    n = _n(param_set)
+    nb = out.numel() // n
+    if out.numel() != nb * n:
+        raise ValueError(f"out: numel {out.numel()} is not a multiple of n={n}")
+    h = pos.numel() // nb if nb else 1
+    if pos.numel() != nb * h or (nb and not 1 <= h <= n):
+        raise ValueError(f"pos: numel {pos.numel()} is not batch*h = {nb}*h with 1 <= h <= {n}")
+    if val.numel() != pos.numel():
+        raise ValueError(f"val: numel {val.numel()} is not pos.numel() = {pos.numel()}")
+    tensors = (out, pos, val)
+    for t in tensors:
+        _batch(t, 1)   # device, dtype, contiguity
+    fn = lib().poly_scatter
+    _run("poly_scatter", tensors, stream,
+         lambda s: fn(out.data_ptr(), pos.data_ptr(), val.data_ptr(), nb, h, _ps(param_set), s))
+    return out
 
 
 def poly_mul_nussbaumer(c, a, b, param_set, ring="q", stream=None):
