@@ -203,6 +203,45 @@ int ntt_mul_kl_shape(int param_set, int l, size_t *split_max_batch, int *waves_p
 int poly_scatter(uint32_t *d_out, const uint32_t *d_pos, const uint32_t *d_val,
                  size_t batch, int h, int param_set, void *stream);
 
+/* qTESLA's rounding [.]_M and the two norm maxima its signer tests, per
+ * polynomial.  For a coefficient x < 2q and the bit count d:
+ *   x' = x mod q
+ *   c  = x' > (q-1)/2 ? x' - q : x'               centred, |c| <= (q-1)/2
+ *   lo = c mod+- 2^d  in (-2^(d-1), 2^(d-1)]      (c & (2^d - 1), minus 2^d if > 2^(d-1))
+ *   hi = (c - lo) >> d                             = (c + 2^(d-1) - 1) >> d, arithmetic shift
+ *   d_w     [batch][n]   entries < 2q, only read ([B][k][n]: pass batch = B*k)
+ *   d_hi    NULL, or [batch][n] bytes: hi, two's complement (the hash's input)
+ *   d_norms NULL, or [batch][2] uint32: { max |c|, max |lo| } of each polynomial
+ * Whichever output is NULL is neither computed nor touched; both NULL with
+ * batch > 0 is NTT_ERR_NULL.  The library keeps no scheme constants: d is the
+ * caller's (qTESLA: 22 / 22 / 24 for ref / p-I / p-III), and the caller
+ * compares the maxima with its own B - S (test_rejection, on z) and
+ * floor(q/2) - E, 2^(d-1) - E (test_correctness, on w_i).  1 <= d <= 30, and
+ * with d_hi the largest hi, ((q-1)/2 + 2^(d-1) - 1) >> d, must fit a signed
+ * byte (<= 127: d >= 16 / 21 / 22 for ref / p-I / p-III's prime),
+ * NTT_ERR_PARAM otherwise.  d_w and d_hi 16-byte aligned, d_norms 8-byte
+ * (NTT_ERR_ALIGN); no two of the three buffers overlap (NTT_ERR_ALIAS).  All
+ * five parameter sets. */
+int poly_round(uint8_t *d_hi, uint32_t *d_norms, const uint32_t *d_w,
+               size_t batch, int d, int param_set, void *stream);
+
+/* poly_mul_ntt_kl with poly_round as its store epilogue: the verifier's
+ * w_i = a_i * z - t_i * c is rounded where it is computed and the full-width
+ * w never reaches memory.  Bit-identical to poly_mul_ntt_kl into a temporary
+ * followed by poly_round over batch * k polynomials:
+ *   d_hi    NULL, or [batch][k][n] bytes
+ *   d_norms NULL, or [batch][k][2] uint32
+ * d_y, d_ahat, d_add, k, l and the n = 1024 / 2048 restriction are
+ * poly_mul_ntt_kl's, the inputs may overlap each other as there; d, NULL
+ * outputs, their alignment and the byte-range rule are poly_round's.  The
+ * outputs overlap no input (d_add included) and not each other
+ * (NTT_ERR_ALIAS).  l = 1 is served by the same kernel: the signer's
+ * w_i = v_i - e_i * c with d_add = v, where only d_norms is wanted.  The
+ * launch shape is ntt_mul_kl_shape(param_set, 2, ...)'s for both l. */
+int poly_mul_ntt_kl_round(uint8_t *d_hi, uint32_t *d_norms, const uint32_t *const *d_y,
+                          const uint32_t *d_ahat, const uint32_t *d_add, size_t batch,
+                          int k, int l, int d, int param_set, void *stream);
+
 /* Nussbaumer negacyclic product (the paper's alternate algorithm): the
  * reference's single-polynomial CPU routine nussbaumer_fft (NTT.cu:167-277,
  * driver test_nussbaumer :1987-2005), batched on the GPU and extended from

@@ -20,6 +20,7 @@
 #include "ntt_latr.hpp"
 #include "ntt_mulk.hpp"
 #include "ntt_mulkl.hpp"
+#include "ntt_round.hpp"
 #include "ntt_internal.h"
 #include "params.hpp"
 #include "pset.hpp"
@@ -357,6 +358,70 @@ bool ranges_overlap(const void *x, size_t xbytes, const void *y, size_t ybytes)
     return a < b + ybytes && b < a + xbytes;
 }
 
+// poly_mul_ntt_kl_round (ntt_mulkl.hpp): LMulKL's launch shape -- workgroup,
+// chunk length and split threshold are poly_mul_ntt_kl's at l = 2, not swept
+// again -- for l = 2 and for l = 1, which runs the same kernel with one y
+template <int PS> struct LMulKLRound {
+    template <int L>
+    static void launch(const MulKLIn<L> &in, const uint32_t *ahat, const uint32_t *add, const RoundOut &ro, size_t batch,
+                       int k, hipStream_t s, const DevInfo &d)
+    {
+        const Launch l = launch_for(OP_MUL, PS, batch, d, MULKL_WG, MULKL_PPW_MAX);
+        const dim3 g(l.grid, batch <= mulkl_split_max(PS) ? (uint32_t)k : 1u), blk(MULKL_WG);
+        if (add) hipLaunchKernelGGL((k_poly_mul_kl_round<PS, L, true>), g, blk, 0, s, in, ahat, add, ro, (uint32_t)batch, (uint32_t)k, l.ppw);
+        else hipLaunchKernelGGL((k_poly_mul_kl_round<PS, L, false>), g, blk, 0, s, in, ahat, add, ro, (uint32_t)batch, (uint32_t)k, l.ppw);
+    }
+    static int run(const uint32_t *const *y, int l, const uint32_t *ahat, const uint32_t *add, const RoundOut &ro, size_t batch,
+                   int k, hipStream_t s, const DevInfo &d)
+    {
+        if constexpr (PS < LARGE_PS0) {
+            if (l == 1) launch<1>(MulKLIn<1>{{y[0]}}, ahat, add, ro, batch, k, s, d);
+            else launch<2>(MulKLIn<2>{{y[0], y[1]}}, ahat, add, ro, batch, k, s, d);
+            return finish_launch();
+        } else {
+            return NTT_ERR_PARAM;
+        }
+    }
+};
+
+// poly_round (ntt_round.hpp): a workgroup per tile of RoundGeom's WAVES
+// kilo-coefficients, up to ROUND_TILES_MAX consecutive tiles each once there
+// are 8 workgroups per CU
+template <int PS> struct LRound {
+    template <bool HI, bool NORMS>
+    static void launch(const uint32_t *w, uint8_t *hi, uint32_t *norms, size_t nwaves, int dbits, hipStream_t s, const DevInfo &d)
+    {
+        using G = RoundGeom<PS>;
+        const size_t ntiles = (nwaves + G::WAVES - 1) / G::WAVES;
+        size_t tiles = ntiles / ((size_t)d.cus * 8);
+        tiles = tiles < 1 ? 1 : (tiles > ROUND_TILES_MAX ? ROUND_TILES_MAX : tiles);
+        hipLaunchKernelGGL((k_poly_round<PS, HI, NORMS>), dim3((uint32_t)((ntiles + tiles - 1) / tiles)), dim3(G::WG), 0, s, w,
+                           (uint32_t *)hi, (uint2 *)norms, nwaves, (uint32_t)dbits, (uint32_t)tiles);
+    }
+    static int run(const uint32_t *w, uint8_t *hi, uint32_t *norms, size_t batch, int dbits, hipStream_t s, const DevInfo &d)
+    {
+        const size_t nwaves = batch * RoundGeom<PS>::WPP;
+        if (hi && norms) launch<true, true>(w, hi, norms, nwaves, dbits, s, d);
+        else if (hi) launch<true, false>(w, hi, norms, nwaves, dbits, s, d);
+        else launch<false, true>(w, hi, norms, nwaves, dbits, s, d);
+        return finish_launch();
+    }
+};
+
+// largest hi of poly_round: it fits a signed byte iff this is <= 127
+uint32_t round_hmax(uint32_t q, int d) { return ((q - 1) / 2 + (1u << (d - 1)) - 1) >> d; }
+
+// poly_round's checks of d and its two outputs (hbytes / nbytes: their sizes);
+// the caller has checked the parameter set and batch > 0
+int check_round_out(const ParamSet *p, const uint8_t *d_hi, const uint32_t *d_norms, int d, size_t hbytes, size_t nbytes)
+{
+    if (!d_hi && !d_norms) return NTT_ERR_NULL;
+    if (d_hi && round_hmax(p->q, d) > 127) return NTT_ERR_PARAM;
+    if ((((uintptr_t)d_hi) & 15u) || (((uintptr_t)d_norms) & 7u)) return NTT_ERR_ALIGN;
+    if (d_hi && d_norms && ranges_overlap(d_hi, hbytes, d_norms, nbytes)) return NTT_ERR_ALIAS;
+    return NTT_OK;
+}
+
 int transform(Xform k, uint32_t *out, const uint32_t *in, size_t batch, int ps, void *stream)
 {
     int rc = check_common(ps, in, batch);
@@ -553,6 +618,58 @@ int poly_scatter(uint32_t *d_out, const uint32_t *d_pos, const uint32_t *d_val, 
     hipLaunchKernelGGL(k_poly_scatter, dim3((uint32_t)batch), dim3(SCATTER_WG), p->n * 4, (hipStream_t)stream, d_pos, d_val,
                        d_out, p->n, p->q, (uint32_t)h);
     return finish_launch();
+}
+
+int poly_round(uint8_t *d_hi, uint32_t *d_norms, const uint32_t *d_w, size_t batch, int d, int ps, void *stream)
+{
+    const ParamSet *p = param_set(ps);
+    if (!p || d < 1 || d > 30) return NTT_ERR_PARAM;
+    if (batch == 0) return NTT_OK;
+    if (!d_w) return NTT_ERR_NULL;
+    if (batch > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
+    const size_t wbytes = batch * p->n * 4, hbytes = batch * p->n, nbytes = batch * 8;
+    int rc;
+    if ((rc = check_round_out(p, d_hi, d_norms, d, hbytes, nbytes)) != NTT_OK) return rc;
+    if (((uintptr_t)d_w) & 15u) return NTT_ERR_ALIGN;
+    if ((d_hi && ranges_overlap(d_hi, hbytes, d_w, wbytes)) || (d_norms && ranges_overlap(d_norms, nbytes, d_w, wbytes)))
+        return NTT_ERR_ALIAS;
+    DevInfo *dev = nullptr;
+    if ((rc = device_ready(&dev)) != NTT_OK) return rc;
+    return dispatch<LRound>(ps, d_w, d_hi, d_norms, batch, d, (hipStream_t)stream, *dev);
+}
+
+int poly_mul_ntt_kl_round(uint8_t *d_hi, uint32_t *d_norms, const uint32_t *const *d_y, const uint32_t *d_ahat,
+                          const uint32_t *d_add, size_t batch, int k, int l, int d, int ps, void *stream)
+{
+    const ParamSet *p = param_set(ps);
+    if (!p || p->n > 2048) return NTT_ERR_PARAM;   // n = 1024 / 2048, as poly_mul_ntt_kl
+    if (k < 1 || k > NTT_MUL_K_MAX || l < 1 || l > NTT_MUL_L_MAX || d < 1 || d > 30) return NTT_ERR_PARAM;
+    if (batch == 0) return NTT_OK;
+    if (!d_y || !d_ahat) return NTT_ERR_NULL;
+    uintptr_t bits = ((uintptr_t)d_ahat) | ((uintptr_t)d_add);
+    for (int j = 0; j < l; j++) {
+        if (!d_y[j]) return NTT_ERR_NULL;
+        bits |= (uintptr_t)d_y[j];
+    }
+    if (batch > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
+    const size_t row = (size_t)p->n * 4, hbytes = batch * k * p->n, nbytes = batch * k * 8;
+    int rc;
+    if ((rc = check_round_out(p, d_hi, d_norms, d, hbytes, nbytes)) != NTT_OK) return rc;
+    if (bits & 3u) return NTT_ERR_ALIGN;
+    // neither output overlaps any input (the addend included: nothing is accumulated in place)
+    const void *outs[2] = {d_hi, d_norms};
+    const size_t obytes[2] = {hbytes, nbytes};
+    for (int o = 0; o < 2; o++) {
+        if (!outs[o]) continue;
+        for (int j = 0; j < l; j++)
+            if (ranges_overlap(outs[o], obytes[o], d_y[j], batch * row)) return NTT_ERR_ALIAS;
+        if (ranges_overlap(outs[o], obytes[o], d_ahat, (size_t)k * l * row)) return NTT_ERR_ALIAS;
+        if (d_add && ranges_overlap(outs[o], obytes[o], d_add, batch * k * row)) return NTT_ERR_ALIAS;
+    }
+    DevInfo *dev = nullptr;
+    if ((rc = device_ready(&dev)) != NTT_OK) return rc;
+    const RoundOut ro = {d_hi, (uint2 *)d_norms, (uint32_t)d};
+    return dispatch<LMulKLRound>(ps, d_y, l, d_ahat, d_add, ro, batch, k, (hipStream_t)stream, *dev);
 }
 
 int poly_mul_nussbaumer(uint32_t *d_c, const uint32_t *d_a, const uint32_t *d_b, size_t batch, int ps, int ring,

@@ -28,10 +28,14 @@
 // are read where they lie.  They may overlap each other and add; none
 // overlaps out (rejected by the entry point).
 //
+// k_poly_mul_kl_round is the same kernel with poly_round (ntt_round.hpp) as
+// its store epilogue: both are ntt_mulkl_body.hpp, which says how.
+//
 // Also here: k_poly_scatter, sparse (position, value) lists -> dense
 // polynomials (qTESLA's challenge c).
 #pragma once
 #include "ntt_mulk.hpp"
+#include "ntt_round.hpp"
 
 namespace qntt {
 
@@ -80,79 +84,38 @@ __device__ __forceinline__ uint32_t mont_dot(const uint32_t (&y)[L], const uint3
     return 4ull * L * P::Q < 1ull << 32 ? v : csub<P::Q2>(v);
 }
 
+// Outputs of the rounding epilogue (poly_mul_ntt_kl_round): hi NULL or
+// [npoly][k][n] bytes, norms NULL or [npoly][k] pairs, d as in poly_round.
+struct RoundOut {
+    uint8_t *hi;
+    uint2 *norms;
+    uint32_t d;
+};
+
 template <int PS, int L, bool ADD>
 __global__ __launch_bounds__(MULKL_WG, MULKL_WAVES_PER_SIMD) void k_poly_mul_kl(const MulKLIn<L> in,
                                                                                 const uint32_t *__restrict__ ahat,
                                                                                 const uint32_t *add, uint32_t *out,
                                                                                 uint32_t npoly, uint32_t k, uint32_t ppw)
 {
-    using P = typename PSel<PS>::T;
-    using LT = Lane<P>;
-    constexpr int SWO = TW2_ENTRIES * 64;   // bit-5 pairs' offset (pairs)
-    __shared__ __attribute__((aligned(16))) uint32_t lds[MULKL_LDS_WORDS];
-    uint2 *ftw2 = reinterpret_cast<uint2 *>(lds + MULKL_WAVES * XPOSE_WORDS);
-    uint2 *itw2 = ftw2 + TW2_WORDS / 2;
-    fill_tw2<PS, false, MULKL_WG>(ftw2);
-    fill_tw2<PS, true, MULKL_WG>(itw2);
-    __syncthreads();
-    const LT Ln;
-    uint32_t *buf = lds + (threadIdx.x >> 6) * XPOSE_WORDS;
+    constexpr bool RND = false;
+    const RoundOut ro = {};
+#include "ntt_mulkl_body.hpp"
+}
 
-    const uint32_t nunits = (npoly + LT::UPW - 1) / LT::UPW;
-    const uint32_t kn = k * P::N;   // words between two polynomials of out / add (<= 2^14)
-    uint32_t u = blockIdx.x * (MULKL_WAVES * ppw) + wave_id();
-#pragma unroll 1
-    for (uint32_t it = 0; it < ppw; ++it, u += MULKL_WAVES) {   // dispatch-ordered chunk (see chunk_loop)
-        if (u >= nunits) break;
-        const bool valid = LT::BIG || Ln.poly(u) < npoly;
-        uint32_t yh[L][32];
-#pragma unroll
-        for (int t = 0; t < L; ++t) {
-            load32(yh[t], in.y[t] + LT::unit_base(u) + Ln.col_load(u, npoly), [](int j) { return LT::S * j; });
-            fwd_pass1<PS, P>(yh[t], Ln.h, ftw2 + SWO + opaque_zero());
-            // transpose addresses recomputed from an opaque lane here and in the
-            // row loop: kept live across the unit they pin ~25 VGPRs (n = 2048: 7 spilled)
-            lds_p1_to_p2<P>(yh[t], buf, LT(opaque_lane()));
-            fwd_pass2<P>(yh[t], ftw2 + opaque_zero(), Ln.lane);
-#pragma unroll
-            for (int j = 0; j < 32; ++j) yh[t][j] = csub<P::Q2>(yh[t][j]);   // [0, 4q) -> [0, 2q), once for all rows
-        }
-        // out / add addressing as in k_poly_mul_k
-        const size_t ubase = (size_t)u * LT::UPW * kn;
-        const uint32_t ooff = LT::BIG ? Ln.brl : Ln.h * kn + Ln.brl;
-        const uint32_t aoff = valid ? ooff : Ln.brl;
-#pragma unroll 1
-        for (uint32_t i = blockIdx.y; i < k; i += gridDim.y) {
-            const uint32_t *pa = ahat + (size_t)i * (L * P::N) + Ln.brl;   // row i: a_i0-hat .. a_i(L-1)-hat, n words each
-            uint32_t r[32];
-#pragma unroll
-            for (int j = 0; j < 32; ++j) {
-                uint32_t yv[L], av[L];
-#pragma unroll
-                for (int t = 0; t < L; ++t) {
-                    yv[t] = yh[t][j];
-                    av[t] = csub<P::Q2>(pa[t * P::N + LT::S * brv5(j)]);   // a-hat < 2q
-                }
-                r[j] = mont_dot<P, L>(yv, av);
-            }
-            inv_pass2<P>(r, itw2 + opaque_zero(), Ln.lane);
-            lds_p2_to_p1<P>(r, buf, LT(opaque_lane()));
-            const size_t rbase = ubase + (size_t)i * P::N;
-            uint32_t ad[ADD ? 32 : 1];
-            if constexpr (ADD) load32(ad, add + rbase + aoff, [](int j) { return LT::S * j; });
-            uint32_t *po = out + rbase + ooff;
-            // stores interleaved with the last stage; with an addend the last
-            // stage leaves [0, 2q) and the sum (< 4q) is reduced here
-            auto emit = [&](int j, uint32_t v) {
-                if constexpr (ADD) v = canon4<P>(v + ad[j]);
-                if (valid) st_out(po + LT::S * j, v);
-            };
-            inv_pass1_head<P>(r, Ln.h, tw_base<PS, true>(), itw2 + SWO + opaque_zero());
-            constexpr uint32_t S0P = cshoup(P::NINV_R, P::Q);
-            constexpr TwPair S1S = csigned_tw(P::C1_R, P::Q);
-            inv_last_stage<P, !ADD>(r, P::NINV_R, S0P, S1S.x, S1S.y, emit);
-        }
-    }
+// poly_mul_ntt_kl_round: k_poly_mul_kl with poly_round as its store epilogue,
+// at the same launch bounds and launch shape.  L = 1 (one y, the signer's
+// w_i = v_i - e_i c with the addend v) is the same body.
+template <int PS, int L, bool ADD>
+__global__ __launch_bounds__(MULKL_WG, MULKL_WAVES_PER_SIMD) void k_poly_mul_kl_round(const MulKLIn<L> in,
+                                                                                      const uint32_t *__restrict__ ahat,
+                                                                                      const uint32_t *add, const RoundOut ro,
+                                                                                      uint32_t npoly, uint32_t k,
+                                                                                      uint32_t ppw)
+{
+    constexpr bool RND = true;
+    uint32_t *const out = nullptr;
+#include "ntt_mulkl_body.hpp"
 }
 
 // poly_scatter: one workgroup per polynomial builds it in LDS -- zero, scatter

@@ -29,6 +29,12 @@
 //                 w_i = a_i z - t_i c in one launch, against the two
 //                 poly_mul_ntt_k launches it replaces (tmp = (-t_i) c, then
 //                 a_i z + tmp accumulated in place); -k K as for 13
+//   -speedgpu 15  poly_round (qTESLA's high bits and norm maxima): (a) alone,
+//                 with both outputs, hi only and norms only, beside
+//                 poly_pointwise over the same coefficients; (b) n <= 2048:
+//                 poly_mul_ntt_kl_round (l = 2) against poly_mul_ntt_kl then
+//                 poly_round; -k K as for 13, -d D bits (default: the set's
+//                 own, 22 / 22 / 24), -leg a|b for one leg only
 //   -param ref|p-I|p-III|p-III-4096|p-III-8192   parameter set (reference:
 //                 compile-time QTESLA set; the n = 4096 / 8192 sets run every
 //                 option but 11, whose Nussbaumer split is n <= 2048)
@@ -72,11 +78,12 @@
 
 static void help_message()
 {
-    printf("usage: ntt_main -speedgpu {4,6,7,8,9,10,11,12,13,14} [-param ref|p-I|p-III|p-III-4096|p-III-8192] [-batch B] [-reps R] [-k K] [-r seed] [-pcie] [-debug]\n");
+    printf("usage: ntt_main -speedgpu {4,6,7,8,9,10,11,12,13,14,15} [-param ref|p-I|p-III|p-III-4096|p-III-8192] [-batch B] [-reps R] [-k K] [-d D] [-leg a|b] [-r seed] [-pcie] [-debug]\n");
 }
 
 struct Opts {
-    int option = 6, ps = NTT_PARAM_REF, reps = 1, k = 0;
+    int option = 6, ps = NTT_PARAM_REF, reps = 1, k = 0, d = 0;
+    char leg = 0;   // -speedgpu 15: 'a' / 'b' for one leg, 0 for both
     size_t batch = 2;
     bool random = false, pcie = false, debug = false;
     uint64_t seed = 0;
@@ -590,6 +597,159 @@ static int run_mul_ntt_kl(const Opts &o)
     return ok ? 0 : 1;
 }
 
+// -speedgpu 15: poly_round.  -speedgpu 13's protocol throughout: random
+// operands, the paths of a leg timed per rep with HIP events on one stream,
+// alternating, after a warm-up; median with (min - max).
+// Leg (a): poly_round alone over `batch` polynomials -- both outputs, hi only,
+// norms only -- and poly_pointwise (12 B per coefficient) over the same
+// coefficients; time and achieved bytes/s of each.
+// Leg (b), n <= 2048: poly_mul_ntt_kl_round (l = 2) against poly_mul_ntt_kl
+// into a temporary followed by poly_round over batch * k polynomials; the
+// outputs of the two paths are compared on the first and last 256 polynomials.
+static int run_round(const Opts &o)
+{
+    uint32_t n, q;
+    NTT_CALL(ntt_param_info(o.ps, &n, &q, nullptr, nullptr, nullptr, nullptr));
+    const int d = o.d > 0 ? o.d : o.ps <= NTT_PARAM_P_I ? 22 : 24;
+    const size_t row = (size_t)n * 4;
+    hipStream_t s;
+    HIP_OK(hipStreamCreate(&s));
+    hipEvent_t ev[5];
+    for (auto &e : ev) HIP_OK(hipEventCreate(&e));
+    auto stats = [](std::vector<double> v, double *lo, double *hi) {
+        std::sort(v.begin(), v.end());
+        *lo = v.front();
+        *hi = v.back();
+        return v[v.size() / 2];
+    };
+    int ok = 1;
+    if (o.leg != 'b') {
+        const size_t coeffs = o.batch * n;
+        uint32_t *d_w, *d_b, *d_c, *d_norms;
+        uint8_t *d_hi;
+        HIP_OK(hipMalloc(&d_w, coeffs * 4));
+        HIP_OK(hipMalloc(&d_b, coeffs * 4));
+        HIP_OK(hipMalloc(&d_c, coeffs * 4));
+        HIP_OK(hipMalloc(&d_hi, coeffs));
+        HIP_OK(hipMalloc(&d_norms, o.batch * 8));
+        NTT_CALL(ntt_fill_uniform(d_w, o.batch, o.ps, o.seed ^ 0x1111, 0, s));
+        NTT_CALL(ntt_fill_uniform(d_b, o.batch, o.ps, o.seed ^ 0x2222, 0, s));
+        auto path = [&](int which) {
+            switch (which) {
+            case 0: NTT_CALL(poly_round(d_hi, d_norms, d_w, o.batch, d, o.ps, s)); break;
+            case 1: NTT_CALL(poly_round(d_hi, nullptr, d_w, o.batch, d, o.ps, s)); break;
+            case 2: NTT_CALL(poly_round(nullptr, d_norms, d_w, o.batch, d, o.ps, s)); break;
+            default: NTT_CALL(poly_pointwise(d_c, d_w, d_b, o.batch, o.ps, s)); break;
+            }
+        };
+        for (int w = 0; w < 3; w++)
+            for (int p = 0; p < 4; p++) path(p);
+        HIP_OK(hipStreamSynchronize(s));
+        const int inner = coeffs < (1u << 24) ? 20 : 1;   // small batches: launches per timed rep (event resolution)
+        std::vector<double> t[4];
+        for (int r = 0; r < o.reps; r++) {
+            HIP_OK(hipEventRecord(ev[0], s));
+            for (int p = 0; p < 4; p++) {
+                for (int i = 0; i < inner; i++) path(p);
+                HIP_OK(hipEventRecord(ev[p + 1], s));
+            }
+            HIP_OK(hipEventSynchronize(ev[4]));
+            for (int p = 0; p < 4; p++) {
+                float ms = 0.f;
+                HIP_OK(hipEventElapsedTime(&ms, ev[p], ev[p + 1]));
+                t[p].push_back(ms / inner);
+            }
+        }
+        const char *name[4] = {"poly_round hi+norms", "poly_round hi      ", "poly_round norms   ", "poly_pointwise     "};
+        const double bytes[4] = {5.0 * coeffs + 8.0 * o.batch, 5.0 * coeffs, 4.0 * coeffs + 8.0 * o.batch, 12.0 * coeffs};
+        printf("\n========================\npoly_round GPU. Batch Size is %zu, d = %d\n========================\n", o.batch, d);
+        for (int p = 0; p < 4; p++) {
+            double lo, hi;
+            const double m = stats(t[p], &lo, &hi);
+            printf("%s : median %.4f ms (min %.4f, max %.4f over %d reps) per launch, %.4e bytes, %.3f TB/s\n", name[p], m, lo,
+                   hi, o.reps, bytes[p], bytes[p] / m / 1e9);
+        }
+        HIP_OK(hipFree(d_w));
+        HIP_OK(hipFree(d_b));
+        HIP_OK(hipFree(d_c));
+        HIP_OK(hipFree(d_hi));
+        HIP_OK(hipFree(d_norms));
+    }
+    if (o.leg != 'a' && n <= 2048) {
+        const int k = o.k > 0 ? o.k : o.ps == NTT_PARAM_REF ? 1 : o.ps == NTT_PARAM_P_I ? 4 : 5;
+        const size_t npoly = o.batch * k;
+        uint32_t *d_z, *d_c, *d_at, *d_tmp, *d_nf, *d_nc;
+        uint8_t *d_hf, *d_hc;
+        HIP_OK(hipMalloc(&d_z, o.batch * row));
+        HIP_OK(hipMalloc(&d_c, o.batch * row));
+        HIP_OK(hipMalloc(&d_at, 2 * k * row));   // [k][2][n]
+        HIP_OK(hipMalloc(&d_tmp, npoly * row));
+        HIP_OK(hipMalloc(&d_hf, npoly * n));
+        HIP_OK(hipMalloc(&d_hc, npoly * n));
+        HIP_OK(hipMalloc(&d_nf, npoly * 8));
+        HIP_OK(hipMalloc(&d_nc, npoly * 8));
+        NTT_CALL(ntt_fill_uniform(d_z, o.batch, o.ps, o.seed ^ 0x3333, 0, s));
+        NTT_CALL(ntt_fill_uniform(d_c, o.batch, o.ps, o.seed ^ 0x4444, 0, s));
+        NTT_CALL(ntt_fill_uniform(d_at, 2 * k, o.ps, o.seed ^ 0x5555, 0, s));
+        const uint32_t *ys[2] = {d_z, d_c};
+        auto fused = [&]() { NTT_CALL(poly_mul_ntt_kl_round(d_hf, d_nf, ys, d_at, nullptr, o.batch, k, 2, d, o.ps, s)); };
+        auto comp = [&]() {
+            NTT_CALL(poly_mul_ntt_kl(d_tmp, ys, d_at, nullptr, o.batch, k, 2, o.ps, s));
+            NTT_CALL(poly_round(d_hc, d_nc, d_tmp, npoly, d, o.ps, s));
+        };
+        for (int w = 0; w < 3; w++) { fused(); comp(); }
+        HIP_OK(hipStreamSynchronize(s));
+        const int inner = npoly * n < (1u << 24) ? 20 : 1;
+        std::vector<double> tf, tc;
+        for (int r = 0; r < o.reps; r++) {
+            HIP_OK(hipEventRecord(ev[0], s));
+            for (int i = 0; i < inner; i++) fused();
+            HIP_OK(hipEventRecord(ev[1], s));
+            for (int i = 0; i < inner; i++) comp();
+            HIP_OK(hipEventRecord(ev[2], s));
+            HIP_OK(hipEventSynchronize(ev[2]));
+            float a = 0.f, b = 0.f;
+            HIP_OK(hipEventElapsedTime(&a, ev[0], ev[1]));
+            HIP_OK(hipEventElapsedTime(&b, ev[1], ev[2]));
+            tf.push_back(a / inner);
+            tc.push_back(b / inner);
+        }
+        double flo, fhi, clo, chi;
+        const double fm = stats(tf, &flo, &fhi), cm = stats(tc, &clo, &chi);
+        const size_t chk = (o.batch < 256 ? o.batch : 256) * k;   // polynomials at the head and at the tail
+        std::vector<uint8_t> hf(chk * n), hc(chk * n);
+        std::vector<uint32_t> nf(chk * 2), nc(chk * 2);
+        for (int part = 0; part < 2 && ok; part++) {
+            const size_t p0 = part ? npoly - chk : 0;
+            HIP_OK(hipMemcpy(hf.data(), d_hf + p0 * n, chk * n, hipMemcpyDeviceToHost));
+            HIP_OK(hipMemcpy(hc.data(), d_hc + p0 * n, chk * n, hipMemcpyDeviceToHost));
+            HIP_OK(hipMemcpy(nf.data(), d_nf + p0 * 2, chk * 8, hipMemcpyDeviceToHost));
+            HIP_OK(hipMemcpy(nc.data(), d_nc + p0 * 2, chk * 8, hipMemcpyDeviceToHost));
+            ok = memcmp(hf.data(), hc.data(), chk * n) == 0 && memcmp(nf.data(), nc.data(), chk * 8) == 0;
+        }
+        printf("\n========================\npoly_mul_ntt_kl_round GPU. Batch Size is %zu, k = %d, l = 2, d = %d\n========================\n",
+               o.batch, k, d);
+        printf("poly_mul_ntt_kl_round        : median %.4f ms (min %.4f, max %.4f over %d reps) per launch, %.3e rows/s\n", fm,
+               flo, fhi, o.reps, (double)npoly / fm * 1e3);
+        printf("poly_mul_ntt_kl + poly_round : median %.4f ms (min %.4f, max %.4f), %.3e rows/s\n", cm, clo, chi,
+               (double)npoly / cm * 1e3);
+        printf("composition / fused          : %.3f\n", cm / fm);
+        printf("fused == poly_mul_ntt_kl + poly_round (hi and norms, first and last %zu polynomials): %s\n", chk,
+               ok ? "Identical." : "Incorrect result.");
+        HIP_OK(hipFree(d_z));
+        HIP_OK(hipFree(d_c));
+        HIP_OK(hipFree(d_at));
+        HIP_OK(hipFree(d_tmp));
+        HIP_OK(hipFree(d_hf));
+        HIP_OK(hipFree(d_hc));
+        HIP_OK(hipFree(d_nf));
+        HIP_OK(hipFree(d_nc));
+    }
+    for (auto &e : ev) HIP_OK(hipEventDestroy(e));
+    HIP_OK(hipStreamDestroy(s));
+    return ok ? 0 : 1;
+}
+
 int main(int argc, char **argv)
 {
     Opts o;
@@ -613,6 +773,8 @@ int main(int argc, char **argv)
         else if (a == "-batch") { o.batch = strtoull(next(), nullptr, 10); i += 2; }
         else if (a == "-reps") { o.reps = atoi(next()); i += 2; }
         else if (a == "-k") { o.k = atoi(next()); i += 2; }
+        else if (a == "-d") { o.d = atoi(next()); i += 2; }
+        else if (a == "-leg") { o.leg = next()[0]; i += 2; }
         else if (a == "-r") { o.random = true; o.seed = strtoull(next(), nullptr, 0); i += 2; }
         else if (a == "-pcie") { o.pcie = true; i += 1; }
         else if (a == "-debug") { o.debug = true; i += 1; }
@@ -662,6 +824,7 @@ int main(int argc, char **argv)
     case 12: return run_latency(o);
     case 13: return run_mul_ntt_k(o);
     case 14: return run_mul_ntt_kl(o);
+    case 15: return run_round(o);
     default: help_message(); return -1;
     }
     return 0;

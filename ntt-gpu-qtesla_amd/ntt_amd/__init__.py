@@ -89,6 +89,9 @@ def lib():
         L.poly_mul_ntt_kl.argtypes = [_vp, ctypes.POINTER(_vp), _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
         L.ntt_mul_kl_shape.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_int)]
         L.poly_scatter.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
+        L.poly_round.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
+        L.poly_mul_ntt_kl_round.argtypes = [_vp, _vp, ctypes.POINTER(_vp), _vp, _vp, _sz, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int, _vp]
         L.poly_mul_nussbaumer.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.ntt_fill_uniform.argtypes = [_vp, _sz, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, _vp]
         L.ntt_last_hip_error.restype = ctypes.c_int
@@ -496,6 +499,89 @@ def poly_scatter(out, pos, val, param_set, stream=None):
     _run("poly_scatter", tensors, stream,
          lambda s: fn(out.data_ptr(), pos.data_ptr(), val.data_ptr(), nb, h, _ps(param_set), s))
     return out
+
+
+def _round_outputs(where: str, hi, norms, npoly: int, n: int, d: int):
+    """poly_round's outputs: hi int8/uint8 [npoly, n] or None, norms int32
+    [npoly, 2] or None, not both None; the tensors given, for _run."""
+    torch = _torch()
+    if hi is None and norms is None:
+        raise ValueError(f"{where}: neither hi nor norms given")
+    if not 1 <= int(d) <= 30:
+        raise ValueError(f"{where}: d = {d}, expected 1 .. 30")
+    outs = []
+    if hi is not None:
+        if not hi.is_cuda:
+            raise ValueError("ntt_amd operates on device tensors only (no CPU fallback)")
+        if hi.dtype not in (torch.int8, torch.uint8):
+            raise TypeError(f"hi: expected int8/uint8 storage, got {hi.dtype}")
+        if not hi.is_contiguous():
+            raise ValueError("hi must be contiguous ([polynomials][n] bytes)")
+        if hi.numel() != npoly * n:
+            raise ValueError(f"hi: numel {hi.numel()} is not polynomials*n = {npoly}*{n}")
+        outs.append(hi)
+    if norms is not None:
+        _batch(norms, 1)   # device, dtype, contiguity
+        if norms.numel() != npoly * 2:
+            raise ValueError(f"norms: numel {norms.numel()} is not polynomials*2 = {npoly}*2")
+        outs.append(norms)
+    return outs
+
+
+def poly_round(w, param_set, d: int, hi=None, norms=None, stream=None):
+    """qTESLA's rounding and norm maxima of the polynomials w [batch, n]
+    (entries < 2q; pass a [B, k, n] tensor as it is): with c the centred
+    coefficient and c = hi * 2^d + lo, lo in (-2^(d-1), 2^(d-1)],
+
+    hi     int8/uint8 [batch, n], the high parts (two's-complement bytes);
+    norms  int32 [batch, 2], (max |c|, max |lo|) of each polynomial.
+
+    Either may be None (not computed), not both.  d is the caller's constant
+    (qTESLA: 22 / 22 / 24 for ref / p-I / p-III); with hi it must leave hi
+    within a signed byte (NTTError otherwise).  Returns (hi, norms)."""
+    n = _n(param_set)
+    nb = _batch(w, n)
+    outs = _round_outputs("poly_round", hi, norms, nb, n, d)
+    fn = lib().poly_round
+    ph = None if hi is None else hi.data_ptr()
+    pn = None if norms is None else norms.data_ptr()
+    _run("poly_round", (w, *outs), stream, lambda s: fn(ph, pn, w.data_ptr(), nb, int(d), _ps(param_set), s))
+    return hi, norms
+
+
+def poly_mul_ntt_kl_round(ys, ahat, param_set, d: int, hi=None, norms=None, add=None, stream=None):
+    """poly_round of poly_mul_ntt_kl(ys, ahat, add) in one launch, the product
+    never stored (qTESLA's verification: the hash's input [w_i]_M straight
+    from z and c; with one y and add = v, the signer's norms of
+    w_i = v_i - e_i c).  ys, ahat and add as poly_mul_ntt_kl; hi is int8/uint8
+    [batch, k, n], norms int32 [batch, k, 2], either may be None.  No output
+    may overlap an input.  Returns (hi, norms)."""
+    n = _n(param_set)
+    ys = tuple(ys)
+    l = len(ys)
+    if not 1 <= l <= MUL_L_MAX:
+        raise ValueError(f"ys: {l} tensors, expected 1 .. {MUL_L_MAX}")
+    nb = ys[0].numel() // n
+    for j, y in enumerate(ys):
+        if y.numel() != nb * n:
+            raise ValueError(f"ys: numel of ys[{j}] = {y.numel()} is not batch*n = {nb}*{n}, one batch for all")
+    k = ahat.numel() // (l * n)
+    if ahat.numel() != k * l * n or not 1 <= k <= MUL_K_MAX:
+        raise ValueError(f"ahat: numel {ahat.numel()} is not k*l*n with 1 <= k <= {MUL_K_MAX} (l={l}, n={n})")
+    if add is not None and add.numel() != nb * k * n:
+        raise ValueError(f"add: numel {add.numel()} is not batch*k*n = {nb}*{k}*{n}")
+    ins = (*ys, ahat) if add is None else (*ys, ahat, add)
+    for t in ins:
+        _batch(t, n)   # device, dtype, contiguity
+    outs = _round_outputs("poly_mul_ntt_kl_round", hi, norms, nb * k, n, d)
+    fn = lib().poly_mul_ntt_kl_round
+    py = (_vp * l)(*[y.data_ptr() for y in ys])   # host array, read during the call only
+    pa = None if add is None else add.data_ptr()
+    ph = None if hi is None else hi.data_ptr()
+    pn = None if norms is None else norms.data_ptr()
+    _run("poly_mul_ntt_kl_round", (*ins, *outs), stream,
+         lambda s: fn(ph, pn, py, ahat.data_ptr(), pa, nb, k, l, int(d), _ps(param_set), s))
+    return hi, norms
 
 
 def poly_mul_nussbaumer(c, a, b, param_set, ring="q", stream=None):
