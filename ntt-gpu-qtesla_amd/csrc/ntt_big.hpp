@@ -127,7 +127,8 @@ __device__ __forceinline__ uint32_t big_wbase(uint32_t lane)
 // part of each offset in an SGPR, `bytes` the bound: accesses past it are
 // dropped / read 0; POL: cache policy, 2 = nontemporal).  A region wider than
 // the 8 KiB immediate range takes one 64-bit VGPR base per 8 KiB as global
-// addresses (ntt_eo.hpp: held across its loop, they spilled).  The one-wave
+// addresses (the even/odd experiment, profiles/r06/experiments/ntt_eo_r06.patch:
+// held across its loop, they spilled).  The one-wave
 // n = 8192 kernels measured no faster with them (4.27 / 4.33 against 4.24 /
 // 4.27 ms per 2^18, profiles/r06/big8192), nor at 12 waves (4.75 / 5.54 ms:
 // 168 VGPRs leave 32 / 171 spilled), so they keep global addresses.
@@ -277,7 +278,7 @@ __device__ __forceinline__ void big_fwd(uint32_t (&r)[BG::R], uint32_t *buf, con
 // back; then the GS bit-5 stage and swap, the GS stages on pos 6 .. L-2 and
 // the last one scaled by S0 (x + y) and S1 (x - y), canonical.
 // store(J, x) takes layout-A register J's canonical result (big_inv: at
-// dpoly + 64 J + lane; ntt_eo.hpp: one parity of an n = 8192 polynomial).
+// dpoly + 64 J + lane; the even/odd experiment: one parity of an n = 8192 polynomial).
 template <class BG, int BMIN, bool WIDE0, uint32_t S0, uint32_t S1V, class Source, class Store>
 __device__ __forceinline__ void big_inv_to(uint32_t (&r)[BG::R], uint32_t *buf, const uint2 *tab, uint32_t h, uint32_t lane,
                                            Source &&source, Store &&store)

@@ -9,13 +9,14 @@
 #include <cstring>
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 
 #include "../../include/qtesla_ntt.h"
 #include "dev_tables.hpp"
+#include "launch_shape.hpp"
 #include "ntt_device.hpp"
 #include "ntt_large.hpp"
 #include "ntt_big.hpp"
-#include "ntt_eo.hpp"
 #include "ntt_lat.hpp"
 #include "ntt_latr.hpp"
 #include "ntt_mulk.hpp"
@@ -91,31 +92,34 @@ int device_ready(DevInfo **out)
     return NTT_OK;
 }
 
-// Launch shape: one workgroup per `ppw * waves` consecutive work units.  ppw
-// grows with the batch (amortising the 16 KiB LDS-table prologue) but never
-// beyond what keeps >= NTT_MIN_WG_PER_CU workgroups per CU in flight.
+// Launch shapes, all by the one rule of launch_shape.hpp.  The n <= 2048 batch
+// kernels: one workgroup per `ppw * waves` consecutive work units (a unit is
+// one n = 2048 polynomial or two n = 1024 polynomials); ppw grows with the
+// batch (amortising the 16 KiB LDS-table prologue) but never beyond what keeps
+// >= NTT_MIN_WG_PER_CU workgroups per CU in flight.
 #ifndef NTT_MIN_WG_PER_CU
 #define NTT_MIN_WG_PER_CU 4   // ppw 4 instead of 8 at 65 536 n=1024 polys: 3-4 % faster (profiles/r02/s4/ab_launch_ppw_p1_65536.log); 2^20 keeps ppw 16
 #endif
 #ifndef NTT_PPW_MAX
 #define NTT_PPW_MAX 16
 #endif
-struct Launch {
-    uint32_t grid, ppw;
-};
-enum Op { OP_XFORM, OP_MUL };
-Launch launch_for(Op op, int ps, size_t npoly, const DevInfo &d, int wg = 0, size_t ppw_max = NTT_PPW_MAX)
+template <int PS>
+LaunchShape batch_shape(size_t npoly, int waves, const DevInfo &d, size_t ppw_max = NTT_PPW_MAX)
 {
-    const size_t upw = param_set(ps)->logn == 11 ? 1 : 2;
-    const size_t units = (npoly + upw - 1) / upw;
-    const size_t waves = (size_t)(wg ? wg : op == OP_MUL ? MUL_WG : NTT_WG) / 64;
-    const size_t min_groups = (size_t)d.cus * NTT_MIN_WG_PER_CU;
-    size_t ppw = units / (waves * min_groups);
-    ppw = ppw < 1 ? 1 : (ppw > ppw_max ? ppw_max : ppw);
-    Launch l;
-    l.grid = (uint32_t)((units + waves * ppw - 1) / (waves * ppw));
-    l.ppw = (uint32_t)ppw;
-    return l;
+    const size_t units = ceil_div(npoly, PSel<PS>::T::LOGN == 11 ? 1 : 2);
+    return launch_shape(units, waves, d.cus, NTT_MIN_WG_PER_CU, ppw_max);
+}
+// n = 4096 / 8192: `per_wg` polynomials per workgroup step, >= 2 workgroups per CU
+LaunchShape large_shape(size_t npoly, int per_wg, const DevInfo &d)
+{
+    return launch_shape(npoly, per_wg, d.cus, 2, NTT_PPW_MAX);
+}
+
+// A runtime choice as a template argument: f(std::bool_constant<v>{})
+template <class F> void with_flag(bool v, F &&f)
+{
+    if (v) f(std::true_type{});
+    else f(std::false_type{});
 }
 
 int check_common(int ps, const void *p, size_t batch)
@@ -135,6 +139,77 @@ bool partial_overlap(const void *x, const void *y, size_t bytes)
     return a < b + bytes && b < a + bytes;
 }
 
+bool ranges_overlap(const void *x, size_t xbytes, const void *y, size_t ybytes)
+{
+    const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
+    return a < b + ybytes && b < a + xbytes;
+}
+
+// The operands (a, b, c) of poly_mul / poly_mul_ntt / poly_pointwise /
+// poly_mul_nussbaumer, each checked in turn (a's NULL, alignment and size
+// before anything of b), then the alignment `mask` the kernel needs beyond a
+// word and c against a and b (equal is in place, a partial overlap is not).
+// An empty batch is NTT_OK: the caller returns on `rc != NTT_OK || batch == 0`.
+int check_abc(int ps, const uint32_t *a, const uint32_t *b, const uint32_t *c, size_t batch, uintptr_t mask = 3u)
+{
+    int rc;
+    if ((rc = check_common(ps, a, batch)) != NTT_OK || batch == 0) return rc;
+    if ((rc = check_common(ps, b, batch)) != NTT_OK) return rc;
+    if ((rc = check_common(ps, c, batch)) != NTT_OK) return rc;
+    if ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & mask) return NTT_ERR_ALIGN;
+    const size_t bytes = batch * param_set(ps)->n * 4;
+    if (partial_overlap(a, c, bytes) || partial_overlap(b, c, bytes)) return NTT_ERR_ALIAS;
+    return NTT_OK;
+}
+
+// The inputs (y_0 .. y_{l-1}, ahat, add) of poly_mul_ntt_k / _kl / _kl_round:
+// l batches of polynomials, the k x l shared rows and the optional addend.
+struct RowOps {
+    const uint32_t *const *y;
+    int l;
+    const uint32_t *ahat, *add;
+    bool null() const
+    {
+        if (!y || !ahat) return true;
+        for (int j = 0; j < l; j++)
+            if (!y[j]) return true;
+        return false;
+    }
+    uintptr_t bits() const   // every address ORed, for the alignment test; after null()
+    {
+        uintptr_t b = ((uintptr_t)ahat) | ((uintptr_t)add);
+        for (int j = 0; j < l; j++) b |= (uintptr_t)y[j];
+        return b;
+    }
+    // [x, x + bytes) against every y_j and ahat (the addend has its own rule per entry point)
+    bool overlap(const void *x, size_t bytes, size_t batch, int k, size_t row) const
+    {
+        for (int j = 0; j < l; j++)
+            if (ranges_overlap(x, bytes, y[j], batch * row)) return true;
+        return ranges_overlap(x, bytes, ahat, (size_t)k * l * row);
+    }
+};
+// their parameter set (n = 1024 / 2048, the sets qTESLA defines), k and l; NULL: NTT_ERR_PARAM
+const ParamSet *row_param_set(int ps, int k, int l)
+{
+    const ParamSet *p = param_set(ps);
+    return p && p->n <= 2048 && k >= 1 && k <= NTT_MUL_K_MAX && l >= 1 && l <= NTT_MUL_L_MAX ? p : nullptr;
+}
+// poly_mul_ntt_k / _kl: PARAM, empty batch (NTT_OK, as check_abc), NULL, ALIGN, SIZE, ALIAS
+int check_mul_kl(const uint32_t *out, const RowOps &o, size_t batch, int k, int ps)
+{
+    const ParamSet *p = row_param_set(ps, k, o.l);
+    if (!p) return NTT_ERR_PARAM;
+    if (batch == 0) return NTT_OK;
+    if (!out || o.null()) return NTT_ERR_NULL;
+    if ((((uintptr_t)out) | o.bits()) & 3u) return NTT_ERR_ALIGN;
+    if (batch > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
+    const size_t row = (size_t)p->n * 4, obytes = batch * k * row;
+    if (o.overlap(out, obytes, batch, k, row)) return NTT_ERR_ALIAS;
+    if (o.add && partial_overlap(o.add, out, obytes)) return NTT_ERR_ALIAS;
+    return NTT_OK;
+}
+
 int finish_launch()
 {
     hipError_t e = hipGetLastError();
@@ -142,25 +217,22 @@ int finish_launch()
     return NTT_OK;
 }
 
-template <template <int> class Launcher, class... Args>
-int dispatch(int ps, Args &&...args)
+// Launcher<ps>::run(args...) for 0 <= ps < NSETS, NTT_ERR_PARAM otherwise
+template <template <int> class Launcher, int NSETS, int PS = 0, class... Args>
+int dispatch(int ps, Args &...args)
 {
-    switch (ps) {
-    case 0: return Launcher<0>::run(args...);
-    case 1: return Launcher<1>::run(args...);
-    case 2: return Launcher<2>::run(args...);
-    case 3: return Launcher<3>::run(args...);
-    case 4: return Launcher<4>::run(args...);
-    default: return NTT_ERR_PARAM;
-    }
+    if constexpr (PS < NSETS) return ps == PS ? Launcher<PS>::run(args...) : dispatch<Launcher, NSETS, PS + 1>(ps, args...);
+    else return NTT_ERR_PARAM;
 }
-
-// n = 4096 / 8192: polynomials per slot and step count, >= 2 workgroups per CU
-template <class LG>
-size_t large_ppw(size_t batch, const DevInfo &d)
+// ... on the current device, made ready first and passed as run's last
+// argument.  NSETS = LARGE_PS0: the entry points that exist for n <= 2048 only
+// (poly_mul_ntt_k and its kin).
+template <template <int> class Launcher, int NSETS = NPARAM_SETS, class... Args>
+int launch(int ps, Args &&...args)
 {
-    size_t ppw = batch / ((size_t)LG::SLOTS * d.cus * 2);
-    return ppw < 1 ? 1 : (ppw > NTT_PPW_MAX ? NTT_PPW_MAX : ppw);
+    DevInfo *d = nullptr;
+    const int rc = device_ready(&d);
+    return rc != NTT_OK ? rc : dispatch<Launcher, NSETS>(ps, args..., *d);
 }
 
 // transform kind: forward / inverse with natural or bit-reversed NTT-domain
@@ -175,43 +247,39 @@ static_assert(LAT_FWD == NTT_OP_FWD && LAT_INV == NTT_OP_INV && LAT_FWD_BR == NT
                   LAT_INV_BR == NTT_OP_INV_BR && LAT_MUL == NTT_OP_MUL && LAT_MUL_NTT == NTT_OP_MUL_NTT &&
                   LAT_FWD_OOP == NTT_OP_FWD_OOP && LAT_INV_OOP == NTT_OP_INV_OOP,
               "ABI op codes");
+// the four transforms as template arguments: f(inverse, bit-reversed order)
+template <class F> void with_xform(Xform k, F &&f)
+{
+    switch (k) {
+    case FWD: f(std::false_type{}, std::false_type{}); break;
+    case INV: f(std::true_type{}, std::false_type{}); break;
+    case FWD_BR: f(std::false_type{}, std::true_type{}); break;
+    case INV_BR: f(std::true_type{}, std::true_type{}); break;
+    case BITREV: break;   // a kernel of its own, where there is one
+    }
+}
 
 template <int PS> struct LXform {
     template <int RB>
     static void launch_latr(Xform k, const uint32_t *in, uint32_t *out, size_t batch, hipStream_t s)
     {
-        const dim3 g((uint32_t)batch), b(LatRGeo<PSel<PS>::T::LOGN, RB>::T);
-        switch (k) {
-        case FWD: hipLaunchKernelGGL((k_ntt_latr<PS, false, false, RB>), g, b, 0, s, in, out); break;
-        case INV: hipLaunchKernelGGL((k_ntt_latr<PS, true, false, RB>), g, b, 0, s, in, out); break;
-        case FWD_BR: hipLaunchKernelGGL((k_ntt_latr<PS, false, true, RB>), g, b, 0, s, in, out); break;
-        case INV_BR: hipLaunchKernelGGL((k_ntt_latr<PS, true, true, RB>), g, b, 0, s, in, out); break;
-        default: break;
-        }
+        with_xform(k, [&](auto inv, auto br) {
+            hipLaunchKernelGGL((k_ntt_latr<PS, decltype(inv)::value, decltype(br)::value, RB>), dim3((uint32_t)batch),
+                               dim3(LatRGeo<PSel<PS>::T::LOGN, RB>::T), 0, s, in, out);
+        });
     }
     static int run(Xform k, const uint32_t *in, uint32_t *out, size_t batch, hipStream_t s, const DevInfo &d)
     {
-#ifdef NTT_LATR_FORCE
-        // A/B builds only: every transform on the radix-2^NTT_LATR_FORCE
-        // workgroup-per-polynomial kernels (ntt_latr.hpp)
-        if (k != BITREV) {
-            launch_latr<NTT_LATR_FORCE>(k, in, out, batch, s);
-            return finish_launch();
-        }
-#endif
         // FWD / INV: in place or out of place (LAT_FWD_OOP / LAT_INV_OOP)
         const int sop = (k == FWD || k == INV) && in != out ? (k == FWD ? LAT_FWD_OOP : LAT_INV_OOP) : (int)k;
         const int rb = k == BITREV ? 0 : lat_radix(PS, sop, batch);
+        const uint32_t nb = (uint32_t)batch;
         if (rb == 2) {
             // small batches: radix-4 passes, one polynomial per n/4-thread workgroup (ntt_lat.hpp)
-            const dim3 g((uint32_t)batch), b(LatGeo<PSel<PS>::T::LOGN>::T);
-            switch (k) {
-            case FWD: hipLaunchKernelGGL((k_ntt_lat<PS, false, false>), g, b, 0, s, in, out); break;
-            case INV: hipLaunchKernelGGL((k_ntt_lat<PS, true, false>), g, b, 0, s, in, out); break;
-            case FWD_BR: hipLaunchKernelGGL((k_ntt_lat<PS, false, true>), g, b, 0, s, in, out); break;
-            case INV_BR: hipLaunchKernelGGL((k_ntt_lat<PS, true, true>), g, b, 0, s, in, out); break;
-            default: break;
-            }
+            with_xform(k, [&](auto inv, auto br) {
+                hipLaunchKernelGGL((k_ntt_lat<PS, decltype(inv)::value, decltype(br)::value>), dim3(nb),
+                                   dim3(LatGeo<PSel<PS>::T::LOGN>::T), 0, s, in, out);
+            });
         } else if (rb == 3) {
             launch_latr<3>(k, in, out, batch, s);   // radix-8 passes, n/8 threads (ntt_latr.hpp)
         } else if (rb == 4) {
@@ -219,144 +287,116 @@ template <int PS> struct LXform {
         } else if constexpr (PS >= LARGE_PS0) {
             // n = 4096 / 8192: one wave per polynomial (ntt_big.hpp); the
             // bit-reversed orders are one launch too (an extra LDS transpose per chunk)
-            const uint32_t nb = (uint32_t)batch;
-            const dim3 gb((uint32_t)(batch < (size_t)d.cus * 64 ? batch : (size_t)d.cus * 64)), bb(512);
-            using BG = Big<PS>;
-            size_t ppw = batch / ((size_t)BG::WAVES * d.cus * 2);
-            ppw = ppw < 1 ? 1 : (ppw > NTT_PPW_MAX ? NTT_PPW_MAX : ppw);
-            const dim3 g((uint32_t)((batch + BG::WAVES * ppw - 1) / (BG::WAVES * ppw))), b(BG::NT);
-            const uint32_t pw = (uint32_t)ppw;
-#ifdef NTT_EO
-            if (PS == LARGE_PS0 + 1 && (k == FWD || k == INV)) {
-                // n = 8192 as two n = 4096 halves, a pair of waves per polynomial (ntt_eo.hpp)
-                size_t pe = batch / ((size_t)EO::NPAIR * d.cus * 2);
-                pe = pe < 1 ? 1 : (pe > NTT_PPW_MAX ? NTT_PPW_MAX : pe);
-                const dim3 ge((uint32_t)((batch + EO::NPAIR * pe - 1) / (EO::NPAIR * pe))), be(EO::BG::NT);
-                if (k == FWD) hipLaunchKernelGGL(k_ntt_fwd_eo, ge, be, 0, s, in, out, nb, (uint32_t)pe);
-                else hipLaunchKernelGGL(k_ntt_inv_eo, ge, be, 0, s, in, out, nb, (uint32_t)pe);
-                return finish_launch();
-            }
-#endif
-            switch (k) {
-            case FWD: hipLaunchKernelGGL((k_ntt_fwd_big<PS, false>), g, b, 0, s, in, out, nb, pw); break;
-            case INV: hipLaunchKernelGGL((k_ntt_inv_big<PS, false>), g, b, 0, s, in, out, nb, pw); break;
-            case FWD_BR: hipLaunchKernelGGL((k_ntt_fwd_big<PS, true>), g, b, 0, s, in, out, nb, pw); break;
-            case INV_BR: hipLaunchKernelGGL((k_ntt_inv_big<PS, true>), g, b, 0, s, in, out, nb, pw); break;
-            case BITREV: hipLaunchKernelGGL(k_bitrev_large<PS>, gb, bb, 0, s, in, out, nb); break;
-            }
+            const LaunchShape l = large_shape(batch, Big<PS>::WAVES, d);
+            const dim3 g(l.grid), b(Big<PS>::NT);
+            with_xform(k, [&](auto inv, auto br) {
+                constexpr bool BR = decltype(br)::value;
+                if constexpr (decltype(inv)::value) hipLaunchKernelGGL((k_ntt_inv_big<PS, BR>), g, b, 0, s, in, out, nb, l.chunk);
+                else hipLaunchKernelGGL((k_ntt_fwd_big<PS, BR>), g, b, 0, s, in, out, nb, l.chunk);
+            });
+            if (k == BITREV)
+                hipLaunchKernelGGL(k_bitrev_large<PS>, dim3(capped_grid(batch, 1, d.cus, 64)), dim3(512), 0, s, in, out, nb);
         } else {
-            const Launch l = launch_for(OP_XFORM, PS, batch, d);
+            const LaunchShape l = batch_shape<PS>(batch, NTT_WG / 64, d);
             const dim3 g(l.grid), b(NTT_WG);
-            const uint32_t nb = (uint32_t)batch;
-            switch (k) {
-            case FWD: hipLaunchKernelGGL((k_ntt_fwd<PS, false>), g, b, 0, s, in, out, nb, l.ppw); break;
-            case INV: hipLaunchKernelGGL((k_ntt_inv<PS, false>), g, b, 0, s, in, out, nb, l.ppw); break;
-            case FWD_BR: hipLaunchKernelGGL((k_ntt_fwd<PS, true>), g, b, 0, s, in, out, nb, l.ppw); break;
-            case INV_BR: hipLaunchKernelGGL((k_ntt_inv<PS, true>), g, b, 0, s, in, out, nb, l.ppw); break;
-            case BITREV: hipLaunchKernelGGL(k_bitrev<PS>, g, b, 0, s, in, out, nb, l.ppw); break;
-            }
+            with_xform(k, [&](auto inv, auto br) {
+                constexpr bool BR = decltype(br)::value;
+                if constexpr (decltype(inv)::value) hipLaunchKernelGGL((k_ntt_inv<PS, BR>), g, b, 0, s, in, out, nb, l.chunk);
+                else hipLaunchKernelGGL((k_ntt_fwd<PS, BR>), g, b, 0, s, in, out, nb, l.chunk);
+            });
+            if (k == BITREV) hipLaunchKernelGGL(k_bitrev<PS>, g, b, 0, s, in, out, nb, l.chunk);
         }
         return finish_launch();
     }
 };
-template <int PS, bool BHAT>
-void launch_mul_large(const uint32_t *a, const uint32_t *b, uint32_t *c, size_t batch, hipStream_t s, const DevInfo &d)
-{
-    using LG = LargeMul<PS, BHAT>;
-    const size_t ppw = large_ppw<LG>(batch, d);
-    const dim3 g((uint32_t)((batch + LG::SLOTS * ppw - 1) / (LG::SLOTS * ppw))), blk(LG::NT);
-    hipLaunchKernelGGL((k_poly_mul_large<PS, BHAT>), g, blk, 0, s, a, b, c, (uint32_t)batch, (uint32_t)ppw);
-}
 template <int PS> struct LMul {
     static int run(const uint32_t *a, const uint32_t *b, uint32_t *c, size_t batch, hipStream_t s, bool bhat,
                    const DevInfo &d)
     {
-        if constexpr (PSel<PS>::T::N <= 4096) {
+        constexpr int N = PSel<PS>::T::N;
+        const uint32_t nb = (uint32_t)batch;
+        if constexpr (N <= 4096) {
             if (batch <= lat_max_batch(PS, bhat ? LAT_MUL_NTT : LAT_MUL)) {
                 // small batches: one product per workgroup (ntt_lat.hpp)
-                const dim3 g((uint32_t)batch), blk(LatGeo<PSel<PS>::T::LOGN>::T);
-                if (bhat) hipLaunchKernelGGL((k_poly_mul_lat<PS, true>), g, blk, 0, s, a, b, c);
-                else hipLaunchKernelGGL((k_poly_mul_lat<PS, false>), g, blk, 0, s, a, b, c);
+                with_flag(bhat, [&](auto bh) {
+                    hipLaunchKernelGGL((k_poly_mul_lat<PS, decltype(bh)::value>), dim3(nb), dim3(LatGeo<PSel<PS>::T::LOGN>::T),
+                                       0, s, a, b, c);
+                });
                 return finish_launch();
             }
         }
-        if constexpr (PS >= LARGE_PS0 && PSel<PS>::T::N == 4096) {
-            // one wave per product (ntt_big.hpp)
-            const int waves = bhat ? big_mul_waves<true>() : big_mul_waves<false>();
-            size_t ppw = batch / ((size_t)waves * d.cus * 2);
-            ppw = ppw < 1 ? 1 : (ppw > NTT_PPW_MAX ? NTT_PPW_MAX : ppw);
-            const dim3 g((uint32_t)((batch + waves * ppw - 1) / (waves * ppw))), blk(waves * 64);
-            if (bhat) hipLaunchKernelGGL((k_poly_mul_big<PS, true>), g, blk, 0, s, a, b, c, (uint32_t)batch, (uint32_t)ppw);
-            else hipLaunchKernelGGL((k_poly_mul_big<PS, false>), g, blk, 0, s, a, b, c, (uint32_t)batch, (uint32_t)ppw);
-            return finish_launch();
-        } else if constexpr (PS >= LARGE_PS0) {
-            if (bhat) launch_mul_large<PS, true>(a, b, c, batch, s, d);
-            else launch_mul_large<PS, false>(a, b, c, batch, s, d);
-            return finish_launch();
-        } else {
-            if (bhat) {
-                const Launch l = launch_for(OP_MUL, PS, batch, d, mul_wg<PS, true>());
-                hipLaunchKernelGGL((k_poly_mul<PS, true>), dim3(l.grid), dim3(mul_wg<PS, true>()), 0, s, a, b, c, (uint32_t)batch, l.ppw);
+        with_flag(bhat, [&](auto bh) {
+            constexpr bool BHAT = decltype(bh)::value;
+            if constexpr (PS >= LARGE_PS0 && N == 4096) {
+                // one wave per product (ntt_big.hpp)
+                constexpr int waves = big_mul_waves<BHAT>();
+                const LaunchShape l = large_shape(batch, waves, d);
+                hipLaunchKernelGGL((k_poly_mul_big<PS, BHAT>), dim3(l.grid), dim3(waves * 64), 0, s, a, b, c, nb, l.chunk);
+            } else if constexpr (PS >= LARGE_PS0) {
+                using LG = LargeMul<PS, BHAT>;
+                const LaunchShape l = large_shape(batch, LG::SLOTS, d);
+                hipLaunchKernelGGL((k_poly_mul_large<PS, BHAT>), dim3(l.grid), dim3(LG::NT), 0, s, a, b, c, nb, l.chunk);
             } else {
-                const Launch l = launch_for(OP_MUL, PS, batch, d, mul_wg<PS, false>());
-                hipLaunchKernelGGL((k_poly_mul<PS, false>), dim3(l.grid), dim3(mul_wg<PS, false>()), 0, s, a, b, c, (uint32_t)batch, l.ppw);
+                constexpr int wg = mul_wg<PS, BHAT>();
+                const LaunchShape l = batch_shape<PS>(batch, wg / 64, d);
+                hipLaunchKernelGGL((k_poly_mul<PS, BHAT>), dim3(l.grid), dim3(wg), 0, s, a, b, c, nb, l.chunk);
             }
-            return finish_launch();
-        }
+        });
+        return finish_launch();
     }
 };
 template <int PS> struct LPw {
     static int run(const uint32_t *a, const uint32_t *b, uint32_t *c, size_t count4, hipStream_t s, const DevInfo &d)
     {
-        size_t g = (count4 + WG - 1) / WG, cap = (size_t)d.cus * 8;
-        hipLaunchKernelGGL(k_pointwise<PS>, dim3((uint32_t)(g < cap ? g : cap)), dim3(WG), 0, s,
-                           (const uint4 *)a, (const uint4 *)b, (uint4 *)c, count4);
+        hipLaunchKernelGGL(k_pointwise<PS>, dim3(capped_grid(count4, WG, d.cus, 8)), dim3(WG), 0, s, (const uint4 *)a,
+                           (const uint4 *)b, (uint4 *)c, count4);
         return finish_launch();
     }
 };
 
-// poly_mul_ntt_k (ntt_mulk.hpp): the batch kernels' launch shape; up to the
-// measured switch batch the rows are spread over gridDim.y
+// poly_mul_ntt_k and its kin: the batch kernels' launch shape
+// with the kernel's own waves and chunk maximum; up to its measured switch
+// batch `split_max` the k rows are spread over gridDim.y
+struct RowShape {
+    dim3 grid;
+    uint32_t ppw;
+};
+template <int PS>
+RowShape row_shape(size_t batch, int k, int waves, size_t ppw_max, size_t split_max, const DevInfo &d)
+{
+    const LaunchShape l = batch_shape<PS>(batch, waves, d, ppw_max);
+    return {dim3(l.grid, batch <= split_max ? (uint32_t)k : 1u), l.chunk};
+}
+
+// poly_mul_ntt_k (ntt_mulk.hpp)
 template <int PS> struct LMulK {
     static int run(const uint32_t *y, const uint32_t *ahat, const uint32_t *add, uint32_t *out, size_t batch, int k,
                    hipStream_t s, const DevInfo &d)
     {
-        if constexpr (PS < LARGE_PS0) {
-            const Launch l = launch_for(OP_MUL, PS, batch, d, MULK_WG, MULK_PPW_MAX);
-            const dim3 g(l.grid, batch <= mulk_split_max(PS) ? (uint32_t)k : 1u), blk(MULK_WG);
-            if (add) hipLaunchKernelGGL((k_poly_mul_k<PS, true>), g, blk, 0, s, y, ahat, add, out, (uint32_t)batch, (uint32_t)k, l.ppw);
-            else hipLaunchKernelGGL((k_poly_mul_k<PS, false>), g, blk, 0, s, y, ahat, add, out, (uint32_t)batch, (uint32_t)k, l.ppw);
-            return finish_launch();
-        } else {
-            return NTT_ERR_PARAM;
-        }
+        const RowShape r = row_shape<PS>(batch, k, MULK_WAVES, MULK_PPW_MAX, mulk_split_max(PS), d);
+        with_flag(add != nullptr, [&](auto ad) {
+            hipLaunchKernelGGL((k_poly_mul_k<PS, decltype(ad)::value>), r.grid, dim3(MULK_WG), 0, s, y, ahat, add, out,
+                               (uint32_t)batch, (uint32_t)k, r.ppw);
+        });
+        return finish_launch();
     }
 };
 
-// poly_mul_ntt_kl, l = 2 (ntt_mulkl.hpp): poly_mul_ntt_k's launch shape with
-// that kernel's workgroup and its own measured switch batch
+// poly_mul_ntt_kl, l = 2 (ntt_mulkl.hpp): that kernel's workgroup and its own
+// measured switch batch
 template <int PS> struct LMulKL {
     static int run(const uint32_t *const *y, const uint32_t *ahat, const uint32_t *add, uint32_t *out, size_t batch, int k,
                    hipStream_t s, const DevInfo &d)
     {
-        if constexpr (PS < LARGE_PS0) {
-            const Launch l = launch_for(OP_MUL, PS, batch, d, MULKL_WG, MULKL_PPW_MAX);
-            const dim3 g(l.grid, batch <= mulkl_split_max(PS) ? (uint32_t)k : 1u), blk(MULKL_WG);
-            const MulKLIn<2> in = {{y[0], y[1]}};
-            if (add) hipLaunchKernelGGL((k_poly_mul_kl<PS, 2, true>), g, blk, 0, s, in, ahat, add, out, (uint32_t)batch, (uint32_t)k, l.ppw);
-            else hipLaunchKernelGGL((k_poly_mul_kl<PS, 2, false>), g, blk, 0, s, in, ahat, add, out, (uint32_t)batch, (uint32_t)k, l.ppw);
-            return finish_launch();
-        } else {
-            return NTT_ERR_PARAM;
-        }
+        const RowShape r = row_shape<PS>(batch, k, MULKL_WAVES, MULKL_PPW_MAX, mulkl_split_max(PS), d);
+        const MulKLIn<2> in = {{y[0], y[1]}};
+        with_flag(add != nullptr, [&](auto ad) {
+            hipLaunchKernelGGL((k_poly_mul_kl<PS, 2, decltype(ad)::value>), r.grid, dim3(MULKL_WG), 0, s, in, ahat, add, out,
+                               (uint32_t)batch, (uint32_t)k, r.ppw);
+        });
+        return finish_launch();
     }
 };
-
-bool ranges_overlap(const void *x, size_t xbytes, const void *y, size_t ybytes)
-{
-    const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
-    return a < b + ybytes && b < a + xbytes;
-}
 
 // poly_mul_ntt_kl_round (ntt_mulkl.hpp): LMulKL's launch shape -- workgroup,
 // chunk length and split threshold are poly_mul_ntt_kl's at l = 2, not swept
@@ -364,23 +404,20 @@ bool ranges_overlap(const void *x, size_t xbytes, const void *y, size_t ybytes)
 template <int PS> struct LMulKLRound {
     template <int L>
     static void launch(const MulKLIn<L> &in, const uint32_t *ahat, const uint32_t *add, const RoundOut &ro, size_t batch,
-                       int k, hipStream_t s, const DevInfo &d)
+                       int k, hipStream_t s, const RowShape &r)
     {
-        const Launch l = launch_for(OP_MUL, PS, batch, d, MULKL_WG, MULKL_PPW_MAX);
-        const dim3 g(l.grid, batch <= mulkl_split_max(PS) ? (uint32_t)k : 1u), blk(MULKL_WG);
-        if (add) hipLaunchKernelGGL((k_poly_mul_kl_round<PS, L, true>), g, blk, 0, s, in, ahat, add, ro, (uint32_t)batch, (uint32_t)k, l.ppw);
-        else hipLaunchKernelGGL((k_poly_mul_kl_round<PS, L, false>), g, blk, 0, s, in, ahat, add, ro, (uint32_t)batch, (uint32_t)k, l.ppw);
+        with_flag(add != nullptr, [&](auto ad) {
+            hipLaunchKernelGGL((k_poly_mul_kl_round<PS, L, decltype(ad)::value>), r.grid, dim3(MULKL_WG), 0, s, in, ahat, add, ro,
+                               (uint32_t)batch, (uint32_t)k, r.ppw);
+        });
     }
     static int run(const uint32_t *const *y, int l, const uint32_t *ahat, const uint32_t *add, const RoundOut &ro, size_t batch,
                    int k, hipStream_t s, const DevInfo &d)
     {
-        if constexpr (PS < LARGE_PS0) {
-            if (l == 1) launch<1>(MulKLIn<1>{{y[0]}}, ahat, add, ro, batch, k, s, d);
-            else launch<2>(MulKLIn<2>{{y[0], y[1]}}, ahat, add, ro, batch, k, s, d);
-            return finish_launch();
-        } else {
-            return NTT_ERR_PARAM;
-        }
+        const RowShape r = row_shape<PS>(batch, k, MULKL_WAVES, MULKL_PPW_MAX, mulkl_split_max(PS), d);
+        if (l == 1) launch<1>(MulKLIn<1>{{y[0]}}, ahat, add, ro, batch, k, s, r);
+        else launch<2>(MulKLIn<2>{{y[0], y[1]}}, ahat, add, ro, batch, k, s, r);
+        return finish_launch();
     }
 };
 
@@ -392,11 +429,9 @@ template <int PS> struct LRound {
     static void launch(const uint32_t *w, uint8_t *hi, uint32_t *norms, size_t nwaves, int dbits, hipStream_t s, const DevInfo &d)
     {
         using G = RoundGeom<PS>;
-        const size_t ntiles = (nwaves + G::WAVES - 1) / G::WAVES;
-        size_t tiles = ntiles / ((size_t)d.cus * 8);
-        tiles = tiles < 1 ? 1 : (tiles > ROUND_TILES_MAX ? ROUND_TILES_MAX : tiles);
-        hipLaunchKernelGGL((k_poly_round<PS, HI, NORMS>), dim3((uint32_t)((ntiles + tiles - 1) / tiles)), dim3(G::WG), 0, s, w,
-                           (uint32_t *)hi, (uint2 *)norms, nwaves, (uint32_t)dbits, (uint32_t)tiles);
+        const LaunchShape l = launch_shape(ceil_div(nwaves, G::WAVES), 1, d.cus, 8, ROUND_TILES_MAX);
+        hipLaunchKernelGGL((k_poly_round<PS, HI, NORMS>), dim3(l.grid), dim3(G::WG), 0, s, w, (uint32_t *)hi, (uint2 *)norms,
+                           nwaves, (uint32_t)dbits, l.chunk);
     }
     static int run(const uint32_t *w, uint8_t *hi, uint32_t *norms, size_t batch, int dbits, hipStream_t s, const DevInfo &d)
     {
@@ -428,23 +463,15 @@ int transform(Xform k, uint32_t *out, const uint32_t *in, size_t batch, int ps, 
     if (rc == NTT_OK && batch) rc = check_common(ps, out, batch);
     if (rc != NTT_OK || batch == 0) return rc;
     if (partial_overlap(in, out, batch * param_set(ps)->n * 4)) return NTT_ERR_ALIAS;
-    DevInfo *d = nullptr;
-    if ((rc = device_ready(&d)) != NTT_OK) return rc;
-    return dispatch<LXform>(ps, k, in, out, batch, (hipStream_t)stream, *d);
+    return launch<LXform>(ps, k, in, out, batch, (hipStream_t)stream);
 }
 
 int mul_common(uint32_t *d_c, const uint32_t *d_a, const uint32_t *d_b, size_t batch, int ps, void *stream,
                bool bhat)
 {
-    int rc;
-    if ((rc = check_common(ps, d_a, batch)) != NTT_OK || batch == 0) return rc;
-    if ((rc = check_common(ps, d_b, batch)) != NTT_OK) return rc;
-    if ((rc = check_common(ps, d_c, batch)) != NTT_OK) return rc;
-    const size_t bytes = batch * param_set(ps)->n * 4;
-    if (partial_overlap(d_a, d_c, bytes) || partial_overlap(d_b, d_c, bytes)) return NTT_ERR_ALIAS;
-    DevInfo *d = nullptr;
-    if ((rc = device_ready(&d)) != NTT_OK) return rc;
-    return dispatch<LMul>(ps, d_a, d_b, d_c, batch, (hipStream_t)stream, bhat, *d);
+    int rc = check_abc(ps, d_a, d_b, d_c, batch);
+    if (rc != NTT_OK || batch == 0) return rc;
+    return launch<LMul>(ps, d_a, d_b, d_c, batch, (hipStream_t)stream, bhat);
 }
 
 }  // namespace
@@ -539,21 +566,9 @@ int poly_mul_ntt(uint32_t *d_c, const uint32_t *d_a, const uint32_t *d_bhat, siz
 int poly_mul_ntt_k(uint32_t *d_out, const uint32_t *d_y, const uint32_t *d_ahat, const uint32_t *d_add, size_t batch,
                    int k, int ps, void *stream)
 {
-    const ParamSet *p = param_set(ps);
-    if (!p || p->n > 2048) return NTT_ERR_PARAM;   // n = 1024 / 2048, the sets qTESLA defines
-    if (k < 1 || k > NTT_MUL_K_MAX) return NTT_ERR_PARAM;
-    if (batch == 0) return NTT_OK;
-    if (!d_out || !d_y || !d_ahat) return NTT_ERR_NULL;
-    if ((((uintptr_t)d_out) | ((uintptr_t)d_y) | ((uintptr_t)d_ahat) | ((uintptr_t)d_add)) & 3u) return NTT_ERR_ALIGN;
-    if (batch > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
-    const size_t row = (size_t)p->n * 4, obytes = batch * k * row;
-    if (ranges_overlap(d_out, obytes, d_y, batch * row) || ranges_overlap(d_out, obytes, d_ahat, k * row))
-        return NTT_ERR_ALIAS;
-    if (d_add && partial_overlap(d_add, d_out, obytes)) return NTT_ERR_ALIAS;
-    int rc;
-    DevInfo *d = nullptr;
-    if ((rc = device_ready(&d)) != NTT_OK) return rc;
-    return dispatch<LMulK>(ps, d_y, d_ahat, d_add, d_out, batch, k, (hipStream_t)stream, *d);
+    int rc = check_mul_kl(d_out, RowOps{&d_y, 1, d_ahat, d_add}, batch, k, ps);
+    if (rc != NTT_OK || batch == 0) return rc;
+    return launch<LMulK, LARGE_PS0>(ps, d_y, d_ahat, d_add, d_out, batch, k, (hipStream_t)stream);
 }
 
 int ntt_mul_k_shape(int ps, size_t *split_max_batch, int *waves_per_workgroup)
@@ -568,28 +583,10 @@ int ntt_mul_k_shape(int ps, size_t *split_max_batch, int *waves_per_workgroup)
 int poly_mul_ntt_kl(uint32_t *d_out, const uint32_t *const *d_y, const uint32_t *d_ahat, const uint32_t *d_add,
                     size_t batch, int k, int l, int ps, void *stream)
 {
-    const ParamSet *p = param_set(ps);
-    if (!p || p->n > 2048) return NTT_ERR_PARAM;   // n = 1024 / 2048, the sets qTESLA defines
-    if (k < 1 || k > NTT_MUL_K_MAX || l < 1 || l > NTT_MUL_L_MAX) return NTT_ERR_PARAM;
-    if (batch == 0) return NTT_OK;
-    if (!d_out || !d_y || !d_ahat) return NTT_ERR_NULL;
-    uintptr_t bits = ((uintptr_t)d_out) | ((uintptr_t)d_ahat) | ((uintptr_t)d_add);
-    for (int j = 0; j < l; j++) {
-        if (!d_y[j]) return NTT_ERR_NULL;
-        bits |= (uintptr_t)d_y[j];
-    }
-    if (bits & 3u) return NTT_ERR_ALIGN;
-    if (batch > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
-    const size_t row = (size_t)p->n * 4, obytes = batch * k * row;
-    for (int j = 0; j < l; j++)
-        if (ranges_overlap(d_out, obytes, d_y[j], batch * row)) return NTT_ERR_ALIAS;
-    if (ranges_overlap(d_out, obytes, d_ahat, (size_t)k * l * row)) return NTT_ERR_ALIAS;
-    if (d_add && partial_overlap(d_add, d_out, obytes)) return NTT_ERR_ALIAS;
+    int rc = check_mul_kl(d_out, RowOps{d_y, l, d_ahat, d_add}, batch, k, ps);
+    if (rc != NTT_OK || batch == 0) return rc;
     if (l == 1) return poly_mul_ntt_k(d_out, d_y[0], d_ahat, d_add, batch, k, ps, stream);
-    int rc;
-    DevInfo *d = nullptr;
-    if ((rc = device_ready(&d)) != NTT_OK) return rc;
-    return dispatch<LMulKL>(ps, d_y, d_ahat, d_add, d_out, batch, k, (hipStream_t)stream, *d);
+    return launch<LMulKL, LARGE_PS0>(ps, d_y, d_ahat, d_add, d_out, batch, k, (hipStream_t)stream);
 }
 
 int ntt_mul_kl_shape(int ps, int l, size_t *split_max_batch, int *waves_per_workgroup)
@@ -633,43 +630,33 @@ int poly_round(uint8_t *d_hi, uint32_t *d_norms, const uint32_t *d_w, size_t bat
     if (((uintptr_t)d_w) & 15u) return NTT_ERR_ALIGN;
     if ((d_hi && ranges_overlap(d_hi, hbytes, d_w, wbytes)) || (d_norms && ranges_overlap(d_norms, nbytes, d_w, wbytes)))
         return NTT_ERR_ALIAS;
-    DevInfo *dev = nullptr;
-    if ((rc = device_ready(&dev)) != NTT_OK) return rc;
-    return dispatch<LRound>(ps, d_w, d_hi, d_norms, batch, d, (hipStream_t)stream, *dev);
+    return launch<LRound>(ps, d_w, d_hi, d_norms, batch, d, (hipStream_t)stream);
 }
 
 int poly_mul_ntt_kl_round(uint8_t *d_hi, uint32_t *d_norms, const uint32_t *const *d_y, const uint32_t *d_ahat,
                           const uint32_t *d_add, size_t batch, int k, int l, int d, int ps, void *stream)
 {
-    const ParamSet *p = param_set(ps);
-    if (!p || p->n > 2048) return NTT_ERR_PARAM;   // n = 1024 / 2048, as poly_mul_ntt_kl
-    if (k < 1 || k > NTT_MUL_K_MAX || l < 1 || l > NTT_MUL_L_MAX || d < 1 || d > 30) return NTT_ERR_PARAM;
+    // poly_round's order, not poly_mul_ntt_kl's: the inputs' alignment after the outputs' checks
+    const ParamSet *p = row_param_set(ps, k, l);
+    if (!p || d < 1 || d > 30) return NTT_ERR_PARAM;
     if (batch == 0) return NTT_OK;
-    if (!d_y || !d_ahat) return NTT_ERR_NULL;
-    uintptr_t bits = ((uintptr_t)d_ahat) | ((uintptr_t)d_add);
-    for (int j = 0; j < l; j++) {
-        if (!d_y[j]) return NTT_ERR_NULL;
-        bits |= (uintptr_t)d_y[j];
-    }
+    const RowOps in = {d_y, l, d_ahat, d_add};
+    if (in.null()) return NTT_ERR_NULL;
     if (batch > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
     const size_t row = (size_t)p->n * 4, hbytes = batch * k * p->n, nbytes = batch * k * 8;
     int rc;
     if ((rc = check_round_out(p, d_hi, d_norms, d, hbytes, nbytes)) != NTT_OK) return rc;
-    if (bits & 3u) return NTT_ERR_ALIGN;
+    if (in.bits() & 3u) return NTT_ERR_ALIGN;
     // neither output overlaps any input (the addend included: nothing is accumulated in place)
     const void *outs[2] = {d_hi, d_norms};
     const size_t obytes[2] = {hbytes, nbytes};
     for (int o = 0; o < 2; o++) {
         if (!outs[o]) continue;
-        for (int j = 0; j < l; j++)
-            if (ranges_overlap(outs[o], obytes[o], d_y[j], batch * row)) return NTT_ERR_ALIAS;
-        if (ranges_overlap(outs[o], obytes[o], d_ahat, (size_t)k * l * row)) return NTT_ERR_ALIAS;
+        if (in.overlap(outs[o], obytes[o], batch, k, row)) return NTT_ERR_ALIAS;
         if (d_add && ranges_overlap(outs[o], obytes[o], d_add, batch * k * row)) return NTT_ERR_ALIAS;
     }
-    DevInfo *dev = nullptr;
-    if ((rc = device_ready(&dev)) != NTT_OK) return rc;
     const RoundOut ro = {d_hi, (uint2 *)d_norms, (uint32_t)d};
-    return dispatch<LMulKLRound>(ps, d_y, l, d_ahat, d_add, ro, batch, k, (hipStream_t)stream, *dev);
+    return launch<LMulKLRound, LARGE_PS0>(ps, d_y, l, d_ahat, d_add, ro, batch, k, (hipStream_t)stream);
 }
 
 int poly_mul_nussbaumer(uint32_t *d_c, const uint32_t *d_a, const uint32_t *d_b, size_t batch, int ps, int ring,
@@ -679,12 +666,7 @@ int poly_mul_nussbaumer(uint32_t *d_c, const uint32_t *d_a, const uint32_t *d_b,
     if ((rc = check_common(ps, d_a, batch)) != NTT_OK) return rc;
     if (ring != NTT_RING_Q && ring != NTT_RING_M32) return NTT_ERR_PARAM;
     if (param_set(ps)->n > 2048) return NTT_ERR_PARAM;   // Nussbaumer splits for n = 1024 / 2048
-    if (batch == 0) return NTT_OK;
-    if ((rc = check_common(ps, d_b, batch)) != NTT_OK) return rc;
-    if ((rc = check_common(ps, d_c, batch)) != NTT_OK) return rc;
-    if ((((uintptr_t)d_a) | ((uintptr_t)d_b) | ((uintptr_t)d_c)) & 15u) return NTT_ERR_ALIGN;
-    const size_t bytes = batch * param_set(ps)->n * 4;
-    if (partial_overlap(d_a, d_c, bytes) || partial_overlap(d_b, d_c, bytes)) return NTT_ERR_ALIAS;
+    if ((rc = check_abc(ps, d_a, d_b, d_c, batch, 15u)) != NTT_OK || batch == 0) return rc;
     DevInfo *d = nullptr;
     if ((rc = device_ready(&d)) != NTT_OK) return rc;
     const int e = nussbaumer_launch(ps, ring, d_a, d_b, d_c, batch, stream, d->cus);
@@ -694,16 +676,9 @@ int poly_mul_nussbaumer(uint32_t *d_c, const uint32_t *d_a, const uint32_t *d_b,
 
 int poly_pointwise(uint32_t *d_c, const uint32_t *d_a, const uint32_t *d_b, size_t batch, int ps, void *stream)
 {
-    int rc;
-    if ((rc = check_common(ps, d_a, batch)) != NTT_OK || batch == 0) return rc;
-    if ((rc = check_common(ps, d_b, batch)) != NTT_OK) return rc;
-    if ((rc = check_common(ps, d_c, batch)) != NTT_OK) return rc;
-    if ((((uintptr_t)d_a) | ((uintptr_t)d_b) | ((uintptr_t)d_c)) & 15u) return NTT_ERR_ALIGN;
-    const size_t count = batch * param_set(ps)->n;
-    if (partial_overlap(d_a, d_c, count * 4) || partial_overlap(d_b, d_c, count * 4)) return NTT_ERR_ALIAS;
-    DevInfo *d = nullptr;
-    if ((rc = device_ready(&d)) != NTT_OK) return rc;
-    return dispatch<LPw>(ps, d_a, d_b, d_c, count / 4, (hipStream_t)stream, *d);
+    int rc = check_abc(ps, d_a, d_b, d_c, batch, 15u);
+    if (rc != NTT_OK || batch == 0) return rc;
+    return launch<LPw>(ps, d_a, d_b, d_c, batch * param_set(ps)->n / 4, (hipStream_t)stream);
 }
 
 int ntt_fill_uniform(uint32_t *d_poly, size_t batch, int ps, uint64_t seed, uint64_t first_poly, void *stream)
@@ -714,9 +689,8 @@ int ntt_fill_uniform(uint32_t *d_poly, size_t batch, int ps, uint64_t seed, uint
     if ((rc = device_ready(&d)) != NTT_OK) return rc;
     const ParamSet *p = param_set(ps);
     const size_t count = batch * p->n;
-    size_t g = (count + WG - 1) / WG, cap = (size_t)d->cus * 16;
-    hipLaunchKernelGGL(k_fill_uniform, dim3((uint32_t)(g < cap ? g : cap)), dim3(WG), 0, (hipStream_t)stream,
-                       d_poly, count, p->q, seed, first_poly * p->n);
+    hipLaunchKernelGGL(k_fill_uniform, dim3(capped_grid(count, WG, d->cus, 16)), dim3(WG), 0, (hipStream_t)stream, d_poly,
+                       count, p->q, seed, first_poly * p->n);
     return finish_launch();
 }
 
@@ -746,14 +720,8 @@ int ntt_sync_expiries(uint32_t *count)
     if (!count) return NTT_ERR_NULL;
     const hipError_t e = hipMemcpyFromSymbol(count, HIP_SYMBOL(g_slot_sync_expired), sizeof(uint32_t), 0,
                                              hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-        t_last_hip = (int)e;
-        return NTT_ERR_HIP;
-    }
-    return NTT_OK;
+    return e != hipSuccess ? hip_err(e) : NTT_OK;
 }
-
-
 
 const char *ntt_strerror(int code)
 {

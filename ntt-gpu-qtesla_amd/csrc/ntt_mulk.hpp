@@ -41,7 +41,7 @@ constexpr int MULK_LDS_WORDS = MULK_WAVES * XPOSE_WORDS + 2 * TW2_WORDS;
 static_assert(2 * MULK_LDS_WORDS * 4 <= 160 * 1024, "two workgroups per CU (160 KiB LDS)");
 static_assert(2 * MULK_WAVES == 4 * MULK_WAVES_PER_SIMD, "two workgroups fill the CU's four SIMDs");
 constexpr int MULK_K_MAX = 8;   // NTT_MUL_K_MAX
-// Units a wave walks per workgroup, at most (launch_for's ppw).  A unit is
+// Units a wave walks per workgroup, at most (launch_shape's chunk).  A unit is
 // k + 1 transforms long, so 4 amortise the table prologue as 16 do in the
 // other kernels, and the shorter workgroups leave a smaller idle tail: against
 // 16, -10 % (p-III, k = 5) / -12 % (p-I, k = 4) at 2^17 and -2 % at 2^20; 2 is

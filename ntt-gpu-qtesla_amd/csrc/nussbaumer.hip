@@ -49,6 +49,7 @@
 #include <type_traits>
 
 #include "../../include/qtesla_ntt.h"
+#include "launch_shape.hpp"
 #include "ntt_internal.h"
 #include "pset.hpp"
 
@@ -795,14 +796,12 @@ extern "C" int nus_debug_stamps(unsigned long long *host, size_t count)
 int nussbaumer_launch(int ps, int ring, const uint32_t *a, const uint32_t *b, uint32_t *c, size_t batch, void *stream,
                       int cus)
 {
-    const size_t per_unit = ps == 2 ? 1 : 2;
-    const size_t units = (batch + per_unit - 1) / per_unit;
-    size_t ppw = units / ((size_t)NUS_PAIRS * (size_t)cus * 2);
-    const size_t pmax = (size_t)((ring == NTT_RING_M32 && ps == 2) ? nus_ppw_max<2, NTT_RING_M32>() : nus_ppw_max<0, NTT_RING_Q>());
-    ppw = ppw < 1 ? 1 : (ppw > pmax ? pmax : ppw);
-    const dim3 grid((uint32_t)((units + NUS_PAIRS * ppw - 1) / (NUS_PAIRS * ppw)));
+    // a unit (one n = 2048 product or two n = 1024 products) per pair of waves, >= 2 workgroups per CU
+    const int pmax = (ring == NTT_RING_M32 && ps == 2) ? nus_ppw_max<2, NTT_RING_M32>() : nus_ppw_max<0, NTT_RING_Q>();
+    const LaunchShape l = launch_shape(ceil_div(batch, ps == 2 ? 1 : 2), NUS_PAIRS, cus, 2, pmax);
+    const dim3 grid(l.grid);
     hipStream_t s = (hipStream_t)stream;
-    const uint32_t nb = (uint32_t)batch, pw = (uint32_t)ppw;
+    const uint32_t nb = (uint32_t)batch, pw = l.chunk;
 #define QNTT_NUS(PSV, RV)                                                                                   \
     if (ps == PSV && ring == RV) {                                                                          \
         hipLaunchKernelGGL((k_nussbaumer<PSV, RV>), grid, dim3(NUS_WG), 0, s, a, b, c, nb, pw);             \

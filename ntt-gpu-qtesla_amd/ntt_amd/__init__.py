@@ -251,12 +251,12 @@ def _stream(stream, device=None):
     return getattr(stream, "cuda_stream", stream)
 
 
-def _batch(t, n: int) -> int:
+def _batch(t, n: int, dtypes=None, storage="int32/uint32") -> int:
     _torch()
     if not t.is_cuda:
         raise ValueError("ntt_amd operates on device tensors only (no CPU fallback)")
-    if t.dtype not in _INT_DTYPES:
-        raise TypeError(f"expected int32/uint32 storage, got {t.dtype}")
+    if t.dtype not in (dtypes or _INT_DTYPES):
+        raise TypeError(f"expected {storage} storage, got {t.dtype}")
     if not t.is_contiguous():
         raise ValueError("tensor must be contiguous (poly-major [batch][n])")
     numel = t.numel()
@@ -442,7 +442,17 @@ def poly_mul_ntt_kl(out, ys, ahat, param_set, add=None, stream=None):
     ys is a sequence of l tensors [batch, n] (separate allocations or views,
     used where they lie), ahat [k, l, n] with k = ahat.numel() // (l * n), out
     and add [batch, k, n]; add may be out (accumulate in place)."""
-    n = _n(param_set)
+    py, pa, nb, k, l, tensors = _rows_operands(_n(param_set), ys, ahat, add, out)
+    fn = lib().poly_mul_ntt_kl
+    _run("poly_mul_ntt_kl", tensors, stream,
+         lambda s: fn(out.data_ptr(), py, ahat.data_ptr(), pa, nb, k, l, _ps(param_set), s))
+    return out
+
+
+def _rows_operands(n: int, ys, ahat, add, out=None):
+    """The operands of poly_mul_ntt_kl / poly_mul_ntt_kl_round, checked: the
+    host array of the ys' pointers (read during the call only), add's pointer
+    or None, batch, k, l and the tensors given, for _run."""
     ys = tuple(ys)
     l = len(ys)
     if not 1 <= l <= MUL_L_MAX:
@@ -454,19 +464,15 @@ def poly_mul_ntt_kl(out, ys, ahat, param_set, add=None, stream=None):
     k = ahat.numel() // (l * n)
     if ahat.numel() != k * l * n or not 1 <= k <= MUL_K_MAX:
         raise ValueError(f"ahat: numel {ahat.numel()} is not k*l*n with 1 <= k <= {MUL_K_MAX} (l={l}, n={n})")
-    if out.numel() != nb * k * n:
+    if out is not None and out.numel() != nb * k * n:
         raise ValueError(f"out: numel {out.numel()} is not batch*k*n = {nb}*{k}*{n}")
     if add is not None and add.numel() != nb * k * n:
         raise ValueError(f"add: numel {add.numel()} is not batch*k*n = {nb}*{k}*{n}")
-    tensors = (out, *ys, ahat) if add is None else (out, *ys, ahat, add)
+    tensors = tuple(t for t in (out, *ys, ahat, add) if t is not None)
     for t in tensors:
         _batch(t, n)   # device, dtype, contiguity
-    fn = lib().poly_mul_ntt_kl
-    py = (_vp * l)(*[y.data_ptr() for y in ys])   # host array, read during the call only
-    pa = None if add is None else add.data_ptr()
-    _run("poly_mul_ntt_kl", tensors, stream,
-         lambda s: fn(out.data_ptr(), py, ahat.data_ptr(), pa, nb, k, l, _ps(param_set), s))
-    return out
+    py = (_vp * l)(*[y.data_ptr() for y in ys])
+    return py, None if add is None else add.data_ptr(), nb, k, l, tensors
 
 
 def mul_kl_shape(param_set, l: int) -> dict:
@@ -511,13 +517,7 @@ def _round_outputs(where: str, hi, norms, npoly: int, n: int, d: int):
         raise ValueError(f"{where}: d = {d}, expected 1 .. 30")
     outs = []
     if hi is not None:
-        if not hi.is_cuda:
-            raise ValueError("ntt_amd operates on device tensors only (no CPU fallback)")
-        if hi.dtype not in (torch.int8, torch.uint8):
-            raise TypeError(f"hi: expected int8/uint8 storage, got {hi.dtype}")
-        if not hi.is_contiguous():
-            raise ValueError("hi must be contiguous ([polynomials][n] bytes)")
-        if hi.numel() != npoly * n:
+        if _batch(hi, 1, (torch.int8, torch.uint8), "int8/uint8") != npoly * n:   # device, dtype, contiguity
             raise ValueError(f"hi: numel {hi.numel()} is not polynomials*n = {npoly}*{n}")
         outs.append(hi)
     if norms is not None:
@@ -557,26 +557,9 @@ def poly_mul_ntt_kl_round(ys, ahat, param_set, d: int, hi=None, norms=None, add=
     [batch, k, n], norms int32 [batch, k, 2], either may be None.  No output
     may overlap an input.  Returns (hi, norms)."""
     n = _n(param_set)
-    ys = tuple(ys)
-    l = len(ys)
-    if not 1 <= l <= MUL_L_MAX:
-        raise ValueError(f"ys: {l} tensors, expected 1 .. {MUL_L_MAX}")
-    nb = ys[0].numel() // n
-    for j, y in enumerate(ys):
-        if y.numel() != nb * n:
-            raise ValueError(f"ys: numel of ys[{j}] = {y.numel()} is not batch*n = {nb}*{n}, one batch for all")
-    k = ahat.numel() // (l * n)
-    if ahat.numel() != k * l * n or not 1 <= k <= MUL_K_MAX:
-        raise ValueError(f"ahat: numel {ahat.numel()} is not k*l*n with 1 <= k <= {MUL_K_MAX} (l={l}, n={n})")
-    if add is not None and add.numel() != nb * k * n:
-        raise ValueError(f"add: numel {add.numel()} is not batch*k*n = {nb}*{k}*{n}")
-    ins = (*ys, ahat) if add is None else (*ys, ahat, add)
-    for t in ins:
-        _batch(t, n)   # device, dtype, contiguity
+    py, pa, nb, k, l, ins = _rows_operands(n, ys, ahat, add)
     outs = _round_outputs("poly_mul_ntt_kl_round", hi, norms, nb * k, n, d)
     fn = lib().poly_mul_ntt_kl_round
-    py = (_vp * l)(*[y.data_ptr() for y in ys])   # host array, read during the call only
-    pa = None if add is None else add.data_ptr()
     ph = None if hi is None else hi.data_ptr()
     pn = None if norms is None else norms.data_ptr()
     _run("poly_mul_ntt_kl_round", (*ins, *outs), stream,

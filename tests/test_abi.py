@@ -55,6 +55,33 @@ def test_error_codes_before_any_gpu_work(ntt):
         ntt.param_info("p-II")
 
 
+def test_first_defect_decides(ntt):
+    """Calls with two defects: the code is that of the check that comes first,
+    each operand in turn (NULL, alignment, size of `a` before anything of `b`).
+    The order is ABI; every call fails validation, so no pointer is used."""
+    L = ntt.lib()
+    E = ntt
+    a, b, c = 0x10000, 0x40010000, 0x80010000
+    big = 1 << 31
+    assert L.poly_mul(c, a + 2, None, 1, 2, None) == E.NTT_ERR_ALIGN          # a misaligned before b NULL
+    assert L.poly_mul(None, a, b + 2, 1, 2, None) == E.NTT_ERR_ALIGN          # b misaligned before c NULL
+    assert L.poly_mul(c, a, None, big, 2, None) == E.NTT_ERR_SIZE             # a's size before b NULL
+    assert L.poly_mul_ntt(c + 1, None, b, big, 3, None) == E.NTT_ERR_NULL     # a NULL first
+    assert L.poly_mul(a + 8, a, None, 1, 5, None) == E.NTT_ERR_PARAM
+    assert L.poly_ntt_oop(None, a + 2, 1, 0, None) == E.NTT_ERR_ALIGN         # the input before the output
+    assert L.poly_ntt_oop(a + 2, None, big, 0, None) == E.NTT_ERR_NULL
+    assert L.poly_pointwise(c, a + 4, None, big, 2, None) == E.NTT_ERR_SIZE   # word-aligned a: its size before b
+    assert L.poly_pointwise(c + 4, a + 8, b, 3, 2, None) == E.NTT_ERR_ALIGN   # 16-byte alignment before aliasing
+    assert L.poly_pointwise(a + 16, a, b, 3, 2, None) == E.NTT_ERR_ALIAS
+    # Nussbaumer: a, then the ring and n, then b and c
+    assert L.poly_mul_nussbaumer(c, a, None, 1, 2, 7, None) == E.NTT_ERR_PARAM    # bad ring before b NULL
+    assert L.poly_mul_nussbaumer(c, None, b, 1, 2, 7, None) == E.NTT_ERR_NULL     # a NULL before the bad ring
+    assert L.poly_mul_nussbaumer(c, a, None, 1, 3, 0, None) == E.NTT_ERR_PARAM    # n = 4096 before b NULL
+    assert L.poly_mul_nussbaumer(c, a, None, 0, 2, 7, None) == E.NTT_ERR_PARAM    # ... and before the empty batch
+    assert L.poly_mul_nussbaumer(c, a + 4, None, 1, 2, 0, None) == E.NTT_ERR_NULL  # b NULL before 16-byte alignment
+    assert L.poly_mul_nussbaumer(a + 16, a, b + 4, 3, 2, 1, None) == E.NTT_ERR_ALIGN
+
+
 def test_param_info(ntt):
     assert ntt.param_info("ref")["q"] == 8404993
     assert ntt.param_info("p-I")["q"] == 343576577 and ntt.param_info("p-I")["n"] == 1024

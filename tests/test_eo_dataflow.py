@@ -1,4 +1,5 @@
-"""CPU model of the even/odd n = 8192 transforms (ntt-gpu-qtesla_amd/csrc/ntt_eo.hpp,
+"""CPU model of the even/odd n = 8192 transforms (an experiment kept as
+profiles/r06/experiments/ntt_eo_r06.patch, which adds csrc/ntt_eo.hpp;
 DESIGN.md §9): a pair of waves per polynomial, wave parity `par` runs the
 n = 4096 transform of x[2i + par] (the validated ntt_big.hpp path, modelled
 in test_big_dataflow.py; here the oracle's n = 4096 transform stands in for

@@ -50,6 +50,19 @@ def test_null_align_size(ntt):
         assert _call(ntt, None, y, ahat, None, 1 << 31, 1, ps) == ntt.NTT_ERR_NULL   # NULL before size
 
 
+def test_first_defect_decides(ntt):
+    """Two defects at once: PARAM, NULL, ALIGN, SIZE, ALIAS in that order (ABI)."""
+    out, y, ahat, add = FAKE, FAR, 2 * FAR, 3 * FAR
+    for ps in (0, 1, 2):
+        assert _call(ntt, None, y + 1, ahat, None, 1, 4, ps) == ntt.NTT_ERR_NULL
+        assert _call(ntt, out + 2, y, None, None, 1 << 31, 4, ps) == ntt.NTT_ERR_NULL
+        assert _call(ntt, out, y, ahat, add + 2, 1 << 31, 4, ps) == ntt.NTT_ERR_ALIGN
+        assert _call(ntt, out, out + 2, ahat, None, 3, 4, ps) == ntt.NTT_ERR_ALIGN   # misaligned and overlapping
+        assert _call(ntt, out, out, ahat, None, 1 << 31, 4, ps) == ntt.NTT_ERR_SIZE
+        assert _call(ntt, None, y, ahat, None, 1, 0, ps) == ntt.NTT_ERR_PARAM
+    assert _call(ntt, None, y + 1, ahat, None, 1, 4, 3) == ntt.NTT_ERR_PARAM
+
+
 def test_alias_rules(ntt):
     for ps in (0, 1, 2):
         n = ntt.param_info(ps)["n"]

@@ -65,6 +65,25 @@ def test_null_align_size(ntt):
         assert _call(ntt, out, (y0, None), ahat, None, 1 << 31, 1, 2, ps) == ntt.NTT_ERR_NULL      # NULL before size
 
 
+def test_first_defect_decides(ntt):
+    """Two defects at once: PARAM, NULL, ALIGN, SIZE, ALIAS in that order (ABI),
+    for l = 2 and for l = 1 (which poly_mul_ntt_k finishes)."""
+    out, y0, y1, ahat, add = FAKE, FAR, 2 * FAR, 3 * FAR, 5 * FAR
+    for ps in (0, 1, 2):
+        for l in (1, 2):
+            assert _call(ntt, None, (y0 + 1, y1), ahat, None, 1, 4, l, ps) == ntt.NTT_ERR_NULL
+            assert _call(ntt, out + 2, (None, y1), ahat, None, 1 << 31, 4, l, ps) == ntt.NTT_ERR_NULL
+            assert _call(ntt, out, (y0, y1), ahat, add + 2, 1 << 31, 4, l, ps) == ntt.NTT_ERR_ALIGN
+            assert _call(ntt, out, (out + 2, y1), ahat, None, 3, 4, l, ps) == ntt.NTT_ERR_ALIGN   # misaligned and overlapping
+            assert _call(ntt, out, (out, y1), ahat, None, 1 << 31, 4, l, ps) == ntt.NTT_ERR_SIZE
+            assert _call(ntt, None, (y0, y1), ahat, None, 1, 0, l, ps) == ntt.NTT_ERR_PARAM
+        assert _call(ntt, None, (y0, y1 + 1), ahat, None, 1, 4, 2, ps) == ntt.NTT_ERR_NULL
+        assert _call(ntt, out, (y0, out), ahat, add + 1, 3, 4, 2, ps) == ntt.NTT_ERR_ALIGN
+        # l = 1 never reads d_y[1]
+        assert _call(ntt, out, (y0, None), ahat, add + 1, 3, 4, 1, ps) == ntt.NTT_ERR_ALIGN
+    assert _call(ntt, None, (y0 + 1, y1), ahat, None, 1, 4, 2, 4) == ntt.NTT_ERR_PARAM
+
+
 def test_alias_rules(ntt):
     for ps in (0, 1, 2):
         n = ntt.param_info(ps)["n"]

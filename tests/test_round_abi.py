@@ -90,8 +90,61 @@ def test_poly_round_validation(ntt, ps):
     assert L.poly_round(hi, norms, w, 0, 0, i, None) == E.NTT_ERR_PARAM
 
 
+@pytest.mark.parametrize("ps", SETS)
+def test_poly_round_first_defect_decides(ntt, ps):
+    """Two defects at once (the order is ABI): PARAM, NULL of w, SIZE, then the
+    outputs (both NULL, d against hi, alignment, hi / norms overlap), then w's
+    alignment and the outputs against w."""
+    L = ntt.lib()
+    E = ntt
+    i, n = ntt.PARAM_SETS[ps], ntt.param_info(ps)["n"]
+    own, lowd = M.OWN_D[ps], MIN_D[ps] - 1
+    b = _bufs()
+    hi, norms, w = b["hi"], b["norms"], b["w"]
+    assert L.poly_round(hi + 4, norms, None, 1, own, i, None) == E.NTT_ERR_NULL
+    assert L.poly_round(hi + 4, norms, w, 1 << 31, own, i, None) == E.NTT_ERR_SIZE
+    assert L.poly_round(None, None, w + 4, 1 << 31, own, i, None) == E.NTT_ERR_SIZE
+    assert L.poly_round(None, None, w + 4, 1, own, i, None) == E.NTT_ERR_NULL
+    assert L.poly_round(hi + 4, norms, w, 1, lowd, i, None) == E.NTT_ERR_PARAM     # d before the outputs' alignment
+    assert L.poly_round(hi + 4, norms, None, 1, 31, i, None) == E.NTT_ERR_PARAM
+    assert L.poly_round(hi + 4, hi, w, 3, own, i, None) == E.NTT_ERR_ALIGN         # alignment before the outputs' overlap
+    assert L.poly_round(hi, hi, w + 4, 3, own, i, None) == E.NTT_ERR_ALIAS         # the outputs' overlap before w's alignment
+    assert L.poly_round(None, w + 8, w + 8, 3, own, i, None) == E.NTT_ERR_ALIGN    # w's alignment before its aliasing
+
+
 def _ys(*ptrs):
     return (ctypes.c_void_p * len(ptrs))(*ptrs)
+
+
+@pytest.mark.parametrize("ps", ("ref", "p-I", "p-III"))
+def test_fused_first_defect_decides(ntt, ps):
+    """poly_mul_ntt_kl_round follows poly_round's order, not poly_mul_ntt_kl's:
+    the inputs' NULLs, SIZE, the outputs' checks, and only then the inputs'
+    alignment and the overlaps."""
+    L = ntt.lib()
+    E = ntt
+    i, n = ntt.PARAM_SETS[ps], ntt.param_info(ps)["n"]
+    own, lowd = M.OWN_D[ps], MIN_D[ps] - 1
+    hi, norms = FAKE, FAKE + FAR
+    y0, y1, ahat, add = (FAKE + j * FAR for j in range(2, 6))
+    bad = _ys(y0, y1 + 2)
+
+    def call(hi=hi, norms=norms, ys=bad, ahat=ahat, add=add, batch=3, k=5, l=2, d=own, ps=i):
+        return L.poly_mul_ntt_kl_round(hi, norms, ys, ahat, add, batch, k, l, d, ps, None)
+
+    assert call() == E.NTT_ERR_ALIGN                         # y_1 misaligned, nothing else
+    assert call(hi=None, norms=None) == E.NTT_ERR_NULL
+    assert call(hi=hi + 4) == E.NTT_ERR_ALIGN
+    assert call(d=lowd) == E.NTT_ERR_PARAM                   # d too small for hi: before y_1's alignment
+    assert call(d=lowd, hi=None) == E.NTT_ERR_ALIGN          # ... accepted without hi: y_1's alignment
+    assert call(batch=1 << 31) == E.NTT_ERR_SIZE
+    assert call(batch=1 << 31, hi=None, norms=None) == E.NTT_ERR_SIZE
+    assert call(ahat=None, hi=None, norms=None) == E.NTT_ERR_NULL
+    assert call(norms=hi) == E.NTT_ERR_ALIAS                 # the outputs' overlap before y_1's alignment
+    assert call(hi=y0) == E.NTT_ERR_ALIGN                    # y_1's alignment before an output over an input
+    assert call(k=9, hi=None, norms=None) == E.NTT_ERR_PARAM
+    assert call(ys=_ys(y0 + 2, None), l=1, hi=None, norms=None) == E.NTT_ERR_NULL   # l = 1 reads d_y[0] only
+    assert call(ys=_ys(y0 + 2, None), l=1) == E.NTT_ERR_ALIGN
 
 
 @pytest.mark.parametrize("ps", ("ref", "p-I", "p-III"))
