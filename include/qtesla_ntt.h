@@ -242,6 +242,67 @@ int poly_mul_ntt_kl_round(uint8_t *d_hi, uint32_t *d_norms, const uint32_t *cons
                           const uint32_t *d_ahat, const uint32_t *d_add, size_t batch,
                           int k, int l, int d, int param_set, void *stream);
 
+/* SHAKE128 / SHAKE256 / qTESLA's cshake*_simple over a batch, one launch --
+ * qTESLA's H and G on the device, so that the hi bytes poly_mul_ntt_kl_round
+ * writes never leave it:
+ *   message b = in0[b][0 .. len0) || in1[b][0 .. len1),   out[b] = outlen bytes
+ *   d_in0 [batch][len0] bytes, d_in1 [batch][len1] bytes, d_out [batch][outlen]
+ * The two segments are used where they lie (qTESLA's c'' = H([w]_M || G(m)):
+ * the hi bytes [batch][k n] and the digests [batch][64] are different buffers;
+ * no interleaving copy).  Either length may be 0, and a pointer whose length
+ * is 0 is not looked at (it may be NULL, misaligned, anywhere).
+ *   algo   NTT_XOF_SHAKE128 (rate 168) or NTT_XOF_SHAKE256 (rate 136)
+ *   cstm   -1: plain SHAKE, domain/pad byte 0x1F.
+ *          0 .. 65535: cshake128_simple / cshake256_simple, i.e. NIST cSHAKE
+ *          with an empty function name N and the customization string S = the
+ *          two bytes of cstm, little-endian: the first absorbed block is
+ *          01 <rate> 01 00 01 10 lo hi (<rate> = A8 / 88) and zeros up to the
+ *          rate, one permutation, then the message with domain byte 0x04.
+ * len0 and len1 are multiples of 8 with len0 + len1 < 2^32 (a message ends on
+ * a 64-bit lane of the sponge); outlen is a multiple of 8 with
+ * 8 <= outlen <= NTT_XOF_OUT_MAX.  There is no param_set: the library keeps
+ * no scheme constants.  Checks, in this order (the first defect decides):
+ *   NTT_ERR_PARAM  unknown algo, cstm outside -1 .. 65535, a bad len0 / len1 /
+ *                  outlen
+ *   batch == 0     NTT_OK, nothing else is looked at
+ *   NTT_ERR_NULL   d_out, or a segment of non-zero length
+ *   NTT_ERR_ALIGN  any of the three pointers not 8-byte aligned
+ *   NTT_ERR_SIZE   batch > 2^31 - 1
+ *   NTT_ERR_ALIAS  d_out overlaps an input (the inputs may overlap each other)
+ * One message per lane: the throughput comes from the batch, and a batch of 1
+ * costs the same serial chain of permutations as a batch of thousands. */
+#define NTT_XOF_SHAKE128 0   /* rate 168 */
+#define NTT_XOF_SHAKE256 1   /* rate 136 */
+#define NTT_XOF_OUT_MAX 512
+int ntt_xof(uint8_t *d_out, size_t outlen, const uint8_t *d_in0, size_t len0,
+            const uint8_t *d_in1, size_t len1, size_t batch, int algo, int cstm, void *stream);
+
+/* qTESLA's Enc(c'): a seed to the h positions and signs of the challenge,
+ * exactly the lists poly_scatter takes.
+ *   d_seed [batch][seedlen] bytes; d_pos, d_val [batch][h] uint32
+ * Each seed on its own, with n and q of param_set (encode_c, restated):
+ *   dmsp = 0;  r = cSHAKE128_simple(168 bytes, cstm = dmsp++, seed);  cnt = 0;  i = 0
+ *   while i < h:
+ *       if cnt > 168 - 3:  r = cSHAKE128_simple(168 bytes, cstm = dmsp++, seed);  cnt = 0
+ *       pos = ((r[cnt] << 8) | r[cnt+1]) & (n - 1)
+ *       if pos not yet taken:  d_pos[i] = pos;  d_val[i] = (r[cnt+2] & 1) ? q - 1 : 1;  i++
+ *       cnt += 3
+ * A block of 168 bytes gives 56 draws.  The loop runs for at most
+ * NTT_CHALLENGE_BLOCKS_MAX blocks (no unbounded loop on the device); with
+ * h <= 128 and n >= 1024 a draw is accepted with probability >= 7/8, so hash
+ * outputs never come near the bound.  Were it reached, the entries not yet
+ * drawn get pos = 0xFFFFFFFF, which poly_scatter ignores, and val = 0.
+ * 1 <= h <= NTT_CHALLENGE_H_MAX; seedlen is a multiple of 8 with
+ * 8 <= seedlen <= 160 (one absorb block; qTESLA: 32).  All five parameter
+ * sets.  Checks, in this order: NTT_ERR_PARAM (param_set, h, seedlen),
+ * batch == 0 (NTT_OK), NTT_ERR_NULL, NTT_ERR_ALIGN (all three pointers 8-byte
+ * aligned), NTT_ERR_SIZE, NTT_ERR_ALIAS (the outputs overlap neither the seeds
+ * nor each other). */
+#define NTT_CHALLENGE_H_MAX 128
+#define NTT_CHALLENGE_BLOCKS_MAX 64
+int poly_challenge(uint32_t *d_pos, uint32_t *d_val, const uint8_t *d_seed,
+                   size_t seedlen, size_t batch, int h, int param_set, void *stream);
+
 /* Nussbaumer negacyclic product (the paper's alternate algorithm): the
  * reference's single-polynomial CPU routine nussbaumer_fft (NTT.cu:167-277,
  * driver test_nussbaumer :1987-2005), batched on the GPU and extended from

@@ -22,6 +22,7 @@
 #include "ntt_mulk.hpp"
 #include "ntt_mulkl.hpp"
 #include "ntt_round.hpp"
+#include "ntt_xof.hpp"
 #include "ntt_internal.h"
 #include "params.hpp"
 #include "pset.hpp"
@@ -242,6 +243,8 @@ static_assert((int)FWD == (int)LAT_FWD && (int)INV == (int)LAT_INV && (int)FWD_B
                   (int)INV_BR == (int)LAT_INV_BR,
               "switch table order");
 static_assert(MULK_K_MAX == NTT_MUL_K_MAX, "ABI row limit");
+static_assert(XOF_RATE128 * 8 == 168 && XOF_RATE256 * 8 == 136 && NTT_XOF_OUT_MAX % 8 == 0, "ABI rates and output limit");
+static_assert(NTT_CHALLENGE_BLOCKS_MAX * CHALLENGE_DRAWS >= 8 * NTT_CHALLENGE_H_MAX, "block bound far above h / (7/8) draws");
 static_assert(MULKL_L_MAX == NTT_MUL_L_MAX && NTT_MUL_L_MAX == 2, "ABI column limit (poly_mul_ntt_kl launches l = 2)");
 static_assert(LAT_FWD == NTT_OP_FWD && LAT_INV == NTT_OP_INV && LAT_FWD_BR == NTT_OP_FWD_BR &&
                   LAT_INV_BR == NTT_OP_INV_BR && LAT_MUL == NTT_OP_MUL && LAT_MUL_NTT == NTT_OP_MUL_NTT &&
@@ -657,6 +660,60 @@ int poly_mul_ntt_kl_round(uint8_t *d_hi, uint32_t *d_norms, const uint32_t *cons
     }
     const RoundOut ro = {d_hi, (uint2 *)d_norms, (uint32_t)d};
     return launch<LMulKLRound, LARGE_PS0>(ps, d_y, l, d_ahat, d_add, ro, batch, k, (hipStream_t)stream);
+}
+
+int ntt_xof(uint8_t *d_out, size_t outlen, const uint8_t *d_in0, size_t len0, const uint8_t *d_in1, size_t len1,
+            size_t batch, int algo, int cstm, void *stream)
+{
+    if ((algo != NTT_XOF_SHAKE128 && algo != NTT_XOF_SHAKE256) || cstm < -1 || cstm > 65535) return NTT_ERR_PARAM;
+    if ((len0 & 7u) || (len1 & 7u) || len0 >= ((size_t)1 << 32) || len1 >= ((size_t)1 << 32) ||
+        len0 + len1 >= ((size_t)1 << 32))
+        return NTT_ERR_PARAM;
+    if ((outlen & 7u) || outlen < 8 || outlen > NTT_XOF_OUT_MAX) return NTT_ERR_PARAM;
+    if (batch == 0) return NTT_OK;
+    // a segment of length 0 is never read: its pointer takes part in no check
+    const uint8_t *in0 = len0 ? d_in0 : nullptr, *in1 = len1 ? d_in1 : nullptr;
+    if (!d_out || (len0 && !in0) || (len1 && !in1)) return NTT_ERR_NULL;
+    if ((((uintptr_t)d_out) | ((uintptr_t)in0) | ((uintptr_t)in1)) & 7u) return NTT_ERR_ALIGN;
+    if (batch > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
+    const size_t obytes = batch * outlen;
+    if ((len0 && ranges_overlap(d_out, obytes, in0, batch * len0)) || (len1 && ranges_overlap(d_out, obytes, in1, batch * len1)))
+        return NTT_ERR_ALIAS;
+    int rc;
+    DevInfo *d = nullptr;
+    if ((rc = device_ready(&d)) != NTT_OK) return rc;
+    const dim3 grid((uint32_t)ceil_div(batch, (size_t)XOF_WG)), wg(XOF_WG);
+    const uint32_t ow = (uint32_t)(outlen / 8), w0 = (uint32_t)(len0 / 8), w1 = (uint32_t)(len1 / 8);
+    if (algo == NTT_XOF_SHAKE128)
+        hipLaunchKernelGGL(k_xof<XOF_RATE128>, grid, wg, 0, (hipStream_t)stream, (uint64_t *)d_out, ow, (const uint64_t *)in0, w0,
+                           (const uint64_t *)in1, w1, (uint32_t)batch, cstm);
+    else
+        hipLaunchKernelGGL(k_xof<XOF_RATE256>, grid, wg, 0, (hipStream_t)stream, (uint64_t *)d_out, ow, (const uint64_t *)in0, w0,
+                           (const uint64_t *)in1, w1, (uint32_t)batch, cstm);
+    return finish_launch();
+}
+
+int poly_challenge(uint32_t *d_pos, uint32_t *d_val, const uint8_t *d_seed, size_t seedlen, size_t batch, int h, int ps,
+                   void *stream)
+{
+    const ParamSet *p = param_set(ps);
+    if (!p || h < 1 || h > NTT_CHALLENGE_H_MAX) return NTT_ERR_PARAM;
+    if ((seedlen & 7u) || seedlen < 8 || seedlen > 160) return NTT_ERR_PARAM;
+    if (batch == 0) return NTT_OK;
+    if (!d_pos || !d_val || !d_seed) return NTT_ERR_NULL;
+    if ((((uintptr_t)d_pos) | ((uintptr_t)d_val) | ((uintptr_t)d_seed)) & 7u) return NTT_ERR_ALIGN;
+    if (batch > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
+    const size_t lbytes = batch * (size_t)h * 4, sbytes = batch * seedlen;
+    if (ranges_overlap(d_pos, lbytes, d_val, lbytes) || ranges_overlap(d_pos, lbytes, d_seed, sbytes) ||
+        ranges_overlap(d_val, lbytes, d_seed, sbytes))
+        return NTT_ERR_ALIAS;
+    int rc;
+    DevInfo *d = nullptr;
+    if ((rc = device_ready(&d)) != NTT_OK) return rc;
+    hipLaunchKernelGGL(k_challenge, dim3((uint32_t)ceil_div(batch, (size_t)CHALLENGE_WG)), dim3(CHALLENGE_WG),
+                       (size_t)p->n / 32 * CHALLENGE_WG * 4, (hipStream_t)stream, d_pos, d_val, (const uint64_t *)d_seed,
+                       (uint32_t)(seedlen / 8), (uint32_t)batch, (uint32_t)h, p->n, p->q, (uint32_t)NTT_CHALLENGE_BLOCKS_MAX);
+    return finish_launch();
 }
 
 int poly_mul_nussbaumer(uint32_t *d_c, const uint32_t *d_a, const uint32_t *d_b, size_t batch, int ps, int ring,

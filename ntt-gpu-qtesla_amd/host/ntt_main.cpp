@@ -35,6 +35,10 @@
 //                 poly_mul_ntt_kl_round (l = 2) against poly_mul_ntt_kl then
 //                 poly_round; -k K as for 13, -d D bits (default: the set's
 //                 own, 22 / 22 / 24), -leg a|b for one leg only
+//   -speedgpu 16  the hashes round a verification, n <= 2048: (a) ntt_xof at the
+//                 set's H shape (SHAKE128 / SHAKE256 over k n + 64 bytes, 32
+//                 out) beside the same round's poly_mul_ntt_kl_round; (b)
+//                 poly_challenge (seed 32, h = 25 / 40) then poly_scatter
 //   -param ref|p-I|p-III|p-III-4096|p-III-8192   parameter set (reference:
 //                 compile-time QTESLA set; the n = 4096 / 8192 sets run every
 //                 option but 11, whose Nussbaumer split is n <= 2048)
@@ -78,12 +82,12 @@
 
 static void help_message()
 {
-    printf("usage: ntt_main -speedgpu {4,6,7,8,9,10,11,12,13,14,15} [-param ref|p-I|p-III|p-III-4096|p-III-8192] [-batch B] [-reps R] [-k K] [-d D] [-leg a|b] [-r seed] [-pcie] [-debug]\n");
+    printf("usage: ntt_main -speedgpu {4,6,7,8,9,10,11,12,13,14,15,16} [-param ref|p-I|p-III|p-III-4096|p-III-8192] [-batch B] [-reps R] [-k K] [-d D] [-leg a|b] [-r seed] [-pcie] [-debug]\n");
 }
 
 struct Opts {
     int option = 6, ps = NTT_PARAM_REF, reps = 1, k = 0, d = 0;
-    char leg = 0;   // -speedgpu 15: 'a' / 'b' for one leg, 0 for both
+    char leg = 0;   // -speedgpu 15 / 16: 'a' / 'b' for one leg, 0 for both
     size_t batch = 2;
     bool random = false, pcie = false, debug = false;
     uint64_t seed = 0;
@@ -750,6 +754,115 @@ static int run_round(const Opts &o)
     return ok ? 0 : 1;
 }
 
+// -speedgpu 16: the two hashes round a verification.  -speedgpu 15's protocol:
+// inputs from the device generator, HIP events on one stream, 3 warm-up
+// rounds, median with (min - max) over the repetitions.
+// Leg (a): ntt_xof at qTESLA's H shape of the set -- SHAKE128 over k n + 64
+// bytes for n = 1024 (p-I: 4 * 1024 + 64), SHAKE256 for n = 2048 (p-III:
+// 5 * 2048 + 64), 32 bytes out -- reading the hi bytes the same round's
+// poly_mul_ntt_kl_round (l = 2) has just written and a separate buffer of
+// digests; time, messages/s, input GB/s of the hash, the product's time and
+// the ratio of the two.
+// Leg (b): poly_challenge on the 32-byte outputs of leg (a) (h = 25 for
+// n = 1024, 40 for n = 2048) followed by poly_scatter, each timed.
+static int run_xof(const Opts &o)
+{
+    uint32_t n, q;
+    NTT_CALL(ntt_param_info(o.ps, &n, &q, nullptr, nullptr, nullptr, nullptr));
+    if (n > 2048) {
+        fprintf(stderr, "-speedgpu 16: qTESLA's H shapes are defined for n = 1024 / 2048\n");
+        return -1;
+    }
+    const int k = o.k > 0 ? o.k : o.ps == NTT_PARAM_REF ? 1 : o.ps == NTT_PARAM_P_I ? 4 : 5;
+    const int d = o.d > 0 ? o.d : o.ps <= NTT_PARAM_P_I ? 22 : 24;
+    const int algo = n == 1024 ? NTT_XOF_SHAKE128 : NTT_XOF_SHAKE256, h = n == 1024 ? 25 : 40;
+    const size_t row = (size_t)n * 4, hlen = (size_t)k * n, glen = 64, outlen = 32;
+    hipStream_t s;
+    HIP_OK(hipStreamCreate(&s));
+    hipEvent_t ev[5];
+    for (auto &e : ev) HIP_OK(hipEventCreate(&e));
+    auto stats = [](std::vector<double> v, double *lo, double *hi) {
+        std::sort(v.begin(), v.end());
+        *lo = v.front();
+        *hi = v.back();
+        return v[v.size() / 2];
+    };
+    // the generator fills whole polynomials: byte buffers are rounded up to n words
+    auto polys = [&](size_t bytes) { return (bytes + row - 1) / row; };
+    uint32_t *d_z, *d_c, *d_at, *d_g, *d_pos, *d_val, *d_dense;
+    uint8_t *d_hi, *d_out;
+    HIP_OK(hipMalloc(&d_z, o.batch * row));
+    HIP_OK(hipMalloc(&d_c, o.batch * row));
+    HIP_OK(hipMalloc(&d_at, 2 * k * row));
+    HIP_OK(hipMalloc(&d_hi, polys(o.batch * hlen) * row));
+    HIP_OK(hipMalloc(&d_g, polys(o.batch * glen) * row));
+    HIP_OK(hipMalloc(&d_out, o.batch * outlen));
+    HIP_OK(hipMalloc(&d_pos, o.batch * h * 4));
+    HIP_OK(hipMalloc(&d_val, o.batch * h * 4));
+    HIP_OK(hipMalloc(&d_dense, o.batch * row));
+    NTT_CALL(ntt_fill_uniform(d_z, o.batch, o.ps, o.seed ^ 0x6666, 0, s));
+    NTT_CALL(ntt_fill_uniform(d_c, o.batch, o.ps, o.seed ^ 0x7777, 0, s));
+    NTT_CALL(ntt_fill_uniform(d_at, 2 * k, o.ps, o.seed ^ 0x8888, 0, s));
+    NTT_CALL(ntt_fill_uniform((uint32_t *)d_hi, polys(o.batch * hlen), o.ps, o.seed ^ 0x9999, 0, s));
+    NTT_CALL(ntt_fill_uniform(d_g, polys(o.batch * glen), o.ps, o.seed ^ 0xAAAA, 0, s));
+    const uint32_t *ys[2] = {d_z, d_c};
+    auto product = [&]() { NTT_CALL(poly_mul_ntt_kl_round(d_hi, nullptr, ys, d_at, nullptr, o.batch, k, 2, d, o.ps, s)); };
+    auto hash = [&]() { NTT_CALL(ntt_xof(d_out, outlen, d_hi, hlen, (const uint8_t *)d_g, glen, o.batch, algo, -1, s)); };
+    auto chal = [&]() { NTT_CALL(poly_challenge(d_pos, d_val, d_out, outlen, o.batch, h, o.ps, s)); };
+    auto scat = [&]() { NTT_CALL(poly_scatter(d_dense, d_pos, d_val, o.batch, h, o.ps, s)); };
+    for (int w = 0; w < 3; w++) { product(); hash(); chal(); scat(); }
+    HIP_OK(hipStreamSynchronize(s));
+    const int inner = o.batch <= 4096 ? 5 : 1;   // small batches: launches per timed rep (event resolution)
+    std::vector<double> t[4];
+    for (int r = 0; r < o.reps; r++) {
+        HIP_OK(hipEventRecord(ev[0], s));
+        for (int i = 0; i < inner; i++) product();
+        HIP_OK(hipEventRecord(ev[1], s));
+        for (int i = 0; i < inner; i++) hash();
+        HIP_OK(hipEventRecord(ev[2], s));
+        for (int i = 0; i < inner; i++) chal();
+        HIP_OK(hipEventRecord(ev[3], s));
+        for (int i = 0; i < inner; i++) scat();
+        HIP_OK(hipEventRecord(ev[4], s));
+        HIP_OK(hipEventSynchronize(ev[4]));
+        for (int p = 0; p < 4; p++) {
+            float ms = 0.f;
+            HIP_OK(hipEventElapsedTime(&ms, ev[p], ev[p + 1]));
+            t[p].push_back(ms / inner);
+        }
+    }
+    double lo[4], hi[4], m[4];
+    for (int p = 0; p < 4; p++) m[p] = stats(t[p], &lo[p], &hi[p]);
+    uint8_t first[32];
+    HIP_OK(hipMemcpy(first, d_out, 32, hipMemcpyDeviceToHost));
+    const double in_bytes = (double)o.batch * (hlen + glen);
+    if (o.leg != 'b') {
+        printf("\n========================\nntt_xof GPU. Batch Size is %zu, %s over %zu + %zu bytes, %zu bytes out\n========================\n",
+               o.batch, algo == NTT_XOF_SHAKE128 ? "SHAKE128" : "SHAKE256", hlen, glen, outlen);
+        printf("ntt_xof                : median %.4f ms (min %.4f, max %.4f over %d reps) per launch, %.3e messages/s, %.2f GB/s in\n",
+               m[1], lo[1], hi[1], o.reps, (double)o.batch / m[1] * 1e3, in_bytes / m[1] / 1e6);
+        printf("poly_mul_ntt_kl_round  : median %.4f ms (min %.4f, max %.4f), k = %d, l = 2, d = %d\n", m[0], lo[0], hi[0], k, d);
+        printf("ntt_xof / product      : %.3f\n", m[1] / m[0]);
+        printf("out[0]                 : ");
+        for (int i = 0; i < 32; i++) printf("%02x", first[i]);
+        printf("\n");
+    }
+    if (o.leg != 'a') {
+        printf("\n========================\npoly_challenge GPU. Batch Size is %zu, seed 32 bytes, h = %d\n========================\n",
+               o.batch, h);
+        printf("poly_challenge         : median %.4f ms (min %.4f, max %.4f over %d reps) per launch, %.3e seeds/s\n", m[2], lo[2],
+               hi[2], o.reps, (double)o.batch / m[2] * 1e3);
+        printf("poly_scatter           : median %.4f ms (min %.4f, max %.4f)\n", m[3], lo[3], hi[3]);
+        printf("challenge + scatter    : %.4f ms\n", m[2] + m[3]);
+    }
+    for (void *p : {(void *)d_z, (void *)d_c, (void *)d_at, (void *)d_hi, (void *)d_g, (void *)d_out, (void *)d_pos, (void *)d_val,
+                    (void *)d_dense})
+        HIP_OK(hipFree(p));
+    for (auto &e : ev) HIP_OK(hipEventDestroy(e));
+    HIP_OK(hipStreamDestroy(s));
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     Opts o;
@@ -825,6 +938,7 @@ int main(int argc, char **argv)
     case 13: return run_mul_ntt_k(o);
     case 14: return run_mul_ntt_kl(o);
     case 15: return run_round(o);
+    case 16: return run_xof(o);
     default: help_message(); return -1;
     }
     return 0;

@@ -92,6 +92,8 @@ def lib():
         L.poly_round.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_mul_ntt_kl_round.argtypes = [_vp, _vp, ctypes.POINTER(_vp), _vp, _vp, _sz, ctypes.c_int, ctypes.c_int,
                                             ctypes.c_int, ctypes.c_int, _vp]
+        L.ntt_xof.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, _vp]
+        L.poly_challenge.argtypes = [_vp, _vp, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_mul_nussbaumer.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.ntt_fill_uniform.argtypes = [_vp, _sz, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, _vp]
         L.ntt_last_hip_error.restype = ctypes.c_int
@@ -565,6 +567,79 @@ def poly_mul_ntt_kl_round(ys, ahat, param_set, d: int, hi=None, norms=None, add=
     _run("poly_mul_ntt_kl_round", (*ins, *outs), stream,
          lambda s: fn(ph, pn, py, ahat.data_ptr(), pa, nb, k, l, int(d), _ps(param_set), s))
     return hi, norms
+
+
+XOF_ALGOS = {"shake128": 0, "shake256": 1}   # NTT_XOF_SHAKE128, NTT_XOF_SHAKE256
+XOF_OUT_MAX = 512          # NTT_XOF_OUT_MAX
+CHALLENGE_H_MAX = 128      # NTT_CHALLENGE_H_MAX
+
+
+def _byte_rows(name: str, t, batch: int) -> int:
+    """Row length of a uint8/int8 device tensor [batch, ...]: a multiple of 8."""
+    torch = _torch()
+    _batch(t, 1, (torch.int8, torch.uint8), "int8/uint8")   # device, dtype, contiguity
+    if t.dim() < 2 or t.shape[0] != batch:
+        raise ValueError(f"{name}: shape {tuple(t.shape)}, expected [{batch}, bytes]")
+    row = int(np.prod(t.shape[1:]))
+    if row % 8:
+        raise ValueError(f"{name}: {row} bytes per message, expected a multiple of 8")
+    return row
+
+
+def xof(out, in0, in1=None, algo="shake256", cstm=None, stream=None):
+    """out[b] = XOF(in0[b] || in1[b]) for every b, one launch: SHAKE128 /
+    SHAKE256 (cstm None) or qTESLA's cshake128_simple / cshake256_simple with
+    the 16-bit customization cstm (qTESLA's H, G and the expansions).
+
+    out, in0 and in1 are int8/uint8 device tensors whose first dimension is
+    the batch ([batch, k, n] hi bytes are taken as they are); in1 may be None
+    (one segment).  Bytes per message: multiples of 8, out's within
+    8 .. 512.  The two segments are read where they lie; out overlaps
+    neither.  Returns out."""
+    if out.dim() < 2:
+        raise ValueError(f"out: shape {tuple(out.shape)}, expected [batch, bytes]")
+    nb = out.shape[0]
+    outlen = _byte_rows("out", out, nb)
+    if not 8 <= outlen <= XOF_OUT_MAX:
+        raise ValueError(f"out: {outlen} bytes per message, expected 8 .. {XOF_OUT_MAX}")
+    len0 = _byte_rows("in0", in0, nb)
+    len1 = 0 if in1 is None else _byte_rows("in1", in1, nb)
+    if len0 + len1 >= 1 << 32:
+        raise ValueError("message of 2^32 bytes or more")
+    if isinstance(algo, str) and algo not in XOF_ALGOS:
+        raise ValueError(f"algo {algo!r}, expected one of {sorted(XOF_ALGOS)}")
+    a = XOF_ALGOS[algo] if isinstance(algo, str) else int(algo)
+    c = -1 if cstm is None else int(cstm)
+    if cstm is not None and not 0 <= c <= 0xFFFF:
+        raise ValueError(f"cstm = {cstm}, expected None or 0 .. 65535")
+    p0 = in0.data_ptr() if len0 else None
+    p1 = in1.data_ptr() if len1 else None
+    tensors = (out, in0) if in1 is None else (out, in0, in1)
+    fn = lib().ntt_xof
+    _run("ntt_xof", tensors, stream, lambda s: fn(out.data_ptr(), outlen, p0, len0, p1, len1, nb, a, c, s))
+    return out
+
+
+def poly_challenge(pos, val, seed, param_set, stream=None):
+    """qTESLA's Enc(c'): seed [batch, seedlen] int8/uint8 (seedlen a multiple
+    of 8 within 8 .. 160) to the challenge's h positions and signs, pos and
+    val int32 [batch, h] with 1 <= h <= 128 -- the lists poly_scatter takes
+    (val is 1 or q - 1).  Returns (pos, val)."""
+    _n(param_set)   # the parameter set exists
+    if pos.dim() != 2 or tuple(val.shape) != tuple(pos.shape):
+        raise ValueError(f"pos / val: shapes {tuple(pos.shape)} / {tuple(val.shape)}, expected two equal [batch, h]")
+    nb, h = pos.shape
+    for t in (pos, val):
+        _batch(t, 1)   # device, dtype, contiguity
+    if not 1 <= h <= CHALLENGE_H_MAX:
+        raise ValueError(f"h = {h}, expected 1 .. {CHALLENGE_H_MAX}")
+    seedlen = _byte_rows("seed", seed, nb)
+    if seed.dim() != 2 or not 8 <= seedlen <= 160:
+        raise ValueError(f"seed: shape {tuple(seed.shape)}, expected [{nb}, 8 .. 160]")
+    fn = lib().poly_challenge
+    _run("poly_challenge", (pos, val, seed), stream,
+         lambda s: fn(pos.data_ptr(), val.data_ptr(), seed.data_ptr(), seedlen, nb, h, _ps(param_set), s))
+    return pos, val
 
 
 def poly_mul_nussbaumer(c, a, b, param_set, ring="q", stream=None):
