@@ -122,6 +122,18 @@ __device__ __forceinline__ uint32_t big_wbase(uint32_t lane)
     const uint32_t h = lane >> 5;
     return ((lane & 31u) ^ (h << 4)) + 1024u * h;
 }
+// the b32 side of chunk C's transpose: its 32 A'' registers <-> the rows
+// (the b128 side is the n = 2048 kernels', xpose_rd128 / xpose_wr128)
+template <class BG, int C>
+__device__ __forceinline__ void big_rows_wr(const uint32_t (&r)[BG::R], uint32_t *buf, uint32_t wb)
+{
+    sfor<32>([&](auto T) { buf[big_waddr(wb, T)] = r[BG::creg(C, T)]; });
+}
+template <class BG, int C>
+__device__ __forceinline__ void big_rows_rd(uint32_t (&r)[BG::R], const uint32_t *buf, uint32_t wb)
+{
+    sfor<32>([&](auto T) { r[BG::creg(C, T)] = buf[big_waddr(wb, T)]; });
+}
 
 // Buffer-resource access (scalar base, one 32-bit VGPR offset, the constant
 // part of each offset in an SGPR, `bytes` the bound: accesses past it are
@@ -157,30 +169,6 @@ template <int NR, class Off>
 __device__ __forceinline__ void load32n(uint32_t (&r)[NR], const uint32_t *src, Off off)
 {
     sfor<NR>([&](auto J) { r[J] = ld_in(src + off(J)); });
-}
-
-// chunk_loop with R registers: workgroup b owns polynomials [b WAVES ppw,
-// (b+1) WAVES ppw), its waves take consecutive ones (dispatch-ordered), the
-// first polynomial's loads are issued before the table prologue.  The kernels'
-// `load` / `process` lambdas are always_inline: the n = 8192 bodies are too
-// large for the inliner's heuristics, and an outlined body takes the register
-// array by reference (in scratch memory)
-template <class BG, class Prologue, class Load, class Process>
-__device__ __forceinline__ void big_loop(uint32_t npoly, uint32_t ppw, Prologue &prologue, Load &load, Process &process)
-{
-    uint32_t r[BG::R];
-    uint32_t u = blockIdx.x * (BG::WAVES * ppw) + wave_id();
-    if (u < npoly) load(r, u);
-    prologue();   // every wave reaches the barrier inside
-    if (u >= npoly) return;
-    process(r, u);
-#pragma unroll 1
-    for (uint32_t i = 1; i < ppw; ++i) {
-        u += BG::WAVES;
-        if (u >= npoly) break;
-        load(r, u);
-        process(r, u);
-    }
 }
 
 template <class BG, bool INV>
@@ -256,16 +244,10 @@ __device__ __forceinline__ void big_fwd(uint32_t (&r)[BG::R], uint32_t *buf, con
         // (not 16 loop-invariant address VGPRs)
         const uint32_t wb = big_wbase(opaque_lane());
         const Lane<P> LB(opaque_lane());   // the n = 2048 b128 read side (Lp = brv6(lane))
-        sfor<32>([&](auto T) { buf[big_waddr(wb, T)] = r[BG::creg(c, T)]; });
+        big_rows_wr<BG, c>(r, buf, wb);
         compiler_fence();
         uint32_t v[32];
-        sfor<8>([&](auto Q) {
-            const uint4 x = *reinterpret_cast<const uint4 *>(buf + LB.rbase + ((4u * Q) ^ LB.rxm));
-            v[4 * Q + 0] = x.x;
-            v[4 * Q + 1] = x.y;
-            v[4 * Q + 2] = x.z;
-            v[4 * Q + 3] = x.w;
-        });
+        xpose_rd128(v, buf, LB);
         compiler_fence();
         fwd_pass2<P, BMIN>(v, tab + BG::TS * c + opaque_zero(), lane);
         sink(C, v);
@@ -292,12 +274,9 @@ __device__ __forceinline__ void big_inv_to(uint32_t (&r)[BG::R], uint32_t *buf, 
         uint32_t v[32];
         source(C, v);
         inv_pass2<P, BMIN, WIDE0>(v, tab + BG::TS * c + opaque_zero(), lane);
-        sfor<8>([&](auto Q) {
-            *reinterpret_cast<uint4 *>(buf + LB.rbase + ((4u * Q) ^ LB.rxm)) =
-                make_uint4(v[4 * Q + 0], v[4 * Q + 1], v[4 * Q + 2], v[4 * Q + 3]);
-        });
+        xpose_wr128(v, buf, LB);
         compiler_fence();
-        sfor<32>([&](auto T) { r[BG::creg(c, T)] = buf[big_waddr(wb, T)]; });
+        big_rows_rd<BG, c>(r, buf, wb);
         compiler_fence();
     });
     // bit-5 stage: GS with the lane-half twiddle, then swap back
@@ -325,13 +304,11 @@ __device__ __forceinline__ void big_inv_to(uint32_t (&r)[BG::R], uint32_t *buf, 
         });
     });
     // last stage (pos L-1): x' = (x + y) S0, y' = (x - y) S1 (S1 = S0 psi^-brv(1))
-    constexpr uint32_t S0P = cshoup(S0, P::Q);
-    constexpr TwPair S1 = csigned_tw(S1V, P::Q);
     sfor<H>([&](auto J) {
         constexpr int j = J;
         const uint32_t x = r[j], y = r[j + H];
-        store(J, csub<P::Q>(shoup_mul<P::Q>(x + y, S0, S0P)));
-        store(std::integral_constant<int, j + H>{}, csub<P::Q>(sshoup_mul<P::Q>(x - y, S1.x, S1.y)));
+        store(J, csub<P::Q>(gs_last_sum<P, S0>(x, y)));
+        store(std::integral_constant<int, j + H>{}, csub<P::Q>(gs_last_diff<P, S1V>(x, y)));
     });
 }
 template <class BG, int BMIN, bool WIDE0, uint32_t S0, uint32_t S1V, class Source>
@@ -421,7 +398,7 @@ __global__ __launch_bounds__(Big<PS>::NT, Big<PS>::OCC) void k_ntt_fwd_big(const
                 constexpr int c = C;
                 const uint32_t wb = big_wbase(opaque_lane());
                 const Lane<P> LB(opaque_lane());
-                sfor<8>([&](auto Q) {
+                sfor<8>([&](auto Q) {   // xpose_wr128, canonicalising on the way
                     *reinterpret_cast<uint4 *>(buf + LB.rbase + ((4u * Q) ^ LB.rxm)) =
                         make_uint4(canon4<P>(v[4 * Q + 0]), canon4<P>(v[4 * Q + 1]), canon4<P>(v[4 * Q + 2]),
                                    canon4<P>(v[4 * Q + 3]));
@@ -432,7 +409,7 @@ __global__ __launch_bounds__(Big<PS>::NT, Big<PS>::OCC) void k_ntt_fwd_big(const
             });
         }
     };
-    big_loop<BG>(npoly, ppw, prologue, load, process);
+    chunk_loop<BG::WAVES, BG::R>(npoly, ppw, prologue, load, process);
 }
 
 // Inverse, natural-order output.  BR = false: natural-order input (layout
@@ -469,21 +446,15 @@ __global__ __launch_bounds__(Big<PS>::NT, Big<PS>::OCC) void k_ntt_inv_big(const
                     constexpr int c = C;
                     const uint32_t wb = big_wbase(opaque_lane());
                     const Lane<typename BG::P> LB(opaque_lane());
-                    sfor<32>([&](auto T) { buf[big_waddr(wb, T)] = r[BG::creg(c, T)]; });
+                    big_rows_wr<BG, c>(r, buf, wb);
                     compiler_fence();
-                    sfor<8>([&](auto Q) {
-                        const uint4 x = *reinterpret_cast<const uint4 *>(buf + LB.rbase + ((4u * Q) ^ LB.rxm));
-                        v[4 * Q + 0] = x.x;
-                        v[4 * Q + 1] = x.y;
-                        v[4 * Q + 2] = x.z;
-                        v[4 * Q + 3] = x.w;
-                    });
+                    xpose_rd128(v, buf, LB);
                     compiler_fence();
                 }
         };
         big_inv<BG, 0, false, BG::PL::NINV, BG::PL::C1>(r, buf, tab, h, lane, source, out + (size_t)u * N);
     };
-    big_loop<BG>(npoly, ppw, prologue, load, process);
+    chunk_loop<BG::WAVES, BG::R>(npoly, ppw, prologue, load, process);
 }
 
 // Fused products with one wave per polynomial (n = 4096; n = 8192's operands
@@ -525,7 +496,7 @@ __global__ __launch_bounds__((BigMul<PS, BHAT>::NT), 2) void k_poly_mul_big(
     using BG = BigMul<PS, BHAT>;
     using P = typename BG::P;
     using PL = typename BG::PL;
-    constexpr int LOGR = mul_logr<2>();   // p-III's prime: the n = 2048 product's residues
+    constexpr int LOGR = MUL_LOGR;   // p-III's prime: the n = 2048 product's residues
     using BM = BaseMul<P, LOGR>;
     static_assert(!BG::CMP_ || MUL_CENT >= (1 << (5 - LOGR)) - 1, "the compact table holds every lane entry pass 2 reads");
     constexpr uint32_t N = PL::N;
@@ -580,7 +551,7 @@ __global__ __launch_bounds__((BigMul<PS, BHAT>::NT), 2) void k_poly_mul_big(
                 c + base);
         }
     };
-    big_loop<BG>(npoly, ppw, prologue, load, process);
+    chunk_loop<BG::WAVES, BG::R>(npoly, ppw, prologue, load, process);
 }
 
 }  // namespace qntt

@@ -92,14 +92,26 @@ __device__ __forceinline__ uint32_t sshoup_mul(uint32_t d, uint32_t ws, uint32_t
 // Forward twiddles are stored NEGATED on the device (wn = 2^32 - w, Shoup
 // companion wp of w): the multiply-add then yields -t directly, so both outputs
 // cost one instruction each (v_sub, v_add3):  x' = a + t,  y' = a - t + 2q.
+// Typed operands (poly_mul's typed forwards, see fwd_pass1_lz): XS / YS = x / y
+// in S form, a signed value in (-2q, 2q); YOS = leave y' in S form (no +2q);
+// RED = reduce x (off for inputs < 2q).  y in S form takes the signed Shoup
+// quotient (centred twiddle (wsn, wps)).
+template <uint32_t Q, bool RED, bool XS, bool YS, bool YOS>
+__device__ __forceinline__ void ct_bfly_t(uint32_t &x, uint32_t &y, uint32_t wn, uint32_t wp)
+{
+    const uint32_t a = !RED ? x : XS ? umin(x, x + 2 * Q) : csub<2 * Q>(x);   // [0, 2q)
+    uint32_t qe;
+    if constexpr (YS) qe = (uint32_t)(((int64_t)(int32_t)y * (int32_t)wp - 0x80000000ll) >> 32);
+    else qe = __umulhi(y, wp);
+    const uint32_t tn = madlo32(qe, Q, y * wn);   // -t, t in [0, 2q)
+    x = a - tn;
+    y = YOS ? a + tn : a + tn + 2 * Q;
+}
+// the plain butterfly, everything unsigned: x, y in [0,4q) -> [0,4q)
 template <uint32_t Q, bool REDUCE = true>
 __device__ __forceinline__ void ct_bfly(uint32_t &x, uint32_t &y, uint32_t wn, uint32_t wp)
 {
-    const uint32_t a = REDUCE ? csub<2 * Q>(x) : x;   // [0,4q) -> [0,2q)
-    const uint32_t qe = __umulhi(y, wp);
-    const uint32_t tn = madlo32(qe, Q, y * wn);           // -t, t in [0,2q)
-    x = a - tn;
-    y = a + tn + 2 * Q;
+    ct_bfly_t<Q, REDUCE, false, false, false>(x, y, wn, wp);
 }
 
 // GS butterfly, inputs in [0,2q): x' = (x+y) mod 2q, y' = (x-y) w in [0,2q).
@@ -141,6 +153,15 @@ __device__ __forceinline__ uint32_t canon4(uint32_t x)
 __host__ __device__ constexpr uint32_t xm_of(uint32_t hi)   // XOR on pos bits 2..4
 {
     return (((hi >> 3) & 1) << 2) | (((hi >> 4) & 1) << 3) | ((((hi >> 2) ^ (hi >> 5)) & 1) << 4);
+}
+
+// x's low `bits` bits reversed (twiddle exponents at compile time, LDS
+// exchange maps of the small-batch kernels at run time)
+__host__ __device__ constexpr uint32_t brv_bits(uint32_t x, int bits)
+{
+    uint32_t r = 0;
+    for (int i = 0; i < bits; ++i) r |= ((x >> i) & 1u) << (bits - 1 - i);
+    return r;
 }
 
 template <class P>
@@ -248,13 +269,12 @@ __device__ __forceinline__ uint32_t wave_id() { return __builtin_amdgcn_readfirs
 
 constexpr int XPOSE_WORDS = 2048;   // per-wave transpose buffer (8 KiB)
 
-// pass-1 arrangement (registers, post-swap for n=2048) -> pass-2 layout
+// The b128 side of the wave-private transpose: the lane's 32 words of the
+// pass-2 layout as 8 x uint4 at buf + rbase + (4c ^ rxm).  Shared by the
+// n = 2048 transposes below and the per-chunk ones of ntt_big.hpp.
 template <class P>
-__device__ __forceinline__ void lds_p1_to_p2(uint32_t (&r)[32], uint32_t *buf, const Lane<P> &L)
+__device__ __forceinline__ void xpose_rd128(uint32_t (&r)[32], const uint32_t *buf, const Lane<P> &L)
 {
-#pragma unroll
-    for (int j = 0; j < 32; ++j) buf[p1_addr<P>(L, j)] = r[j];
-    compiler_fence();
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
         const uint4 v = *reinterpret_cast<const uint4 *>(buf + L.rbase + ((4u * c) ^ L.rxm));
@@ -263,6 +283,24 @@ __device__ __forceinline__ void lds_p1_to_p2(uint32_t (&r)[32], uint32_t *buf, c
         r[4 * c + 2] = v.z;
         r[4 * c + 3] = v.w;
     }
+}
+template <class P>
+__device__ __forceinline__ void xpose_wr128(const uint32_t (&r)[32], uint32_t *buf, const Lane<P> &L)
+{
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+        *reinterpret_cast<uint4 *>(buf + L.rbase + ((4u * c) ^ L.rxm)) =
+            make_uint4(r[4 * c + 0], r[4 * c + 1], r[4 * c + 2], r[4 * c + 3]);
+}
+
+// pass-1 arrangement (registers, post-swap for n=2048) -> pass-2 layout
+template <class P>
+__device__ __forceinline__ void lds_p1_to_p2(uint32_t (&r)[32], uint32_t *buf, const Lane<P> &L)
+{
+#pragma unroll
+    for (int j = 0; j < 32; ++j) buf[p1_addr<P>(L, j)] = r[j];
+    compiler_fence();
+    xpose_rd128(r, buf, L);
     compiler_fence();
 }
 
@@ -270,10 +308,7 @@ __device__ __forceinline__ void lds_p1_to_p2(uint32_t (&r)[32], uint32_t *buf, c
 template <class P>
 __device__ __forceinline__ void lds_p2_to_p1(uint32_t (&r)[32], uint32_t *buf, const Lane<P> &L)
 {
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-        *reinterpret_cast<uint4 *>(buf + L.rbase + ((4u * c) ^ L.rxm)) =
-            make_uint4(r[4 * c + 0], r[4 * c + 1], r[4 * c + 2], r[4 * c + 3]);
+    xpose_wr128(r, buf, L);
     compiler_fence();
 #pragma unroll
     for (int j = 0; j < 32; ++j) r[j] = buf[p1_addr<P>(L, j)];
@@ -288,6 +323,15 @@ __device__ __forceinline__ constexpr uint32_t brv5(int j)
 // ------------------------------------------------------------------------
 // twiddle access
 // ------------------------------------------------------------------------
+// the __constant__ twiddle table of a parameter set and direction (n <= 2048)
+template <int PS, bool INV>
+__device__ __forceinline__ const uint2 *tw_table()
+{
+    if constexpr (PS == 0) return INV ? c_inv0 : c_fwd0;
+    else if constexpr (PS == 1) return INV ? c_inv1 : c_fwd1;
+    else return INV ? c_inv2 : c_fwd2;
+}
+
 // Table base + an opaque wave-uniform zero: every uniform twiddle read below
 // becomes an s_load_dwordx{2,8,16} with an immediate offset, re-issued per
 // work unit instead of ~126 hoisted words pinning registers.
@@ -295,9 +339,7 @@ template <int PS, bool INV>
 __device__ __forceinline__ const uint2 *tw_base()
 {
     const uint32_t z = opaque_zero();
-    if constexpr (PS == 0) return (INV ? c_inv0 : c_fwd0) + z;
-    else if constexpr (PS == 1) return (INV ? c_inv1 : c_fwd1) + z;
-    else return (INV ? c_inv2 : c_fwd2) + z;
+    return tw_table<PS, INV>() + z;
 }
 
 // Per-lane pass-2 twiddles live in a per-workgroup LDS table, lane-major
@@ -414,12 +456,6 @@ __device__ __forceinline__ void fwd_pass1(uint32_t (&r)[32], uint32_t h, const u
 // addresses it pays for: -1.4 % (p-III) / -2.2 % (p-I); alone +1.5 % / +0.9 %
 // (profiles/r03/ab_polymul_*.log).  In poly_ntt (HBM-bound) it was -0.6 %
 // p-III, 0 p-I (profiles/r03/ab_fwd_lazybias.log) and is not used there.
-__host__ __device__ constexpr uint32_t cbrv32(uint32_t x, int bits)
-{
-    uint32_t r = 0;
-    for (int i = 0; i < bits; i++) r |= ((x >> i) & 1u) << (bits - 1 - i);
-    return r;
-}
 // (-ws mod 2^32, wps) of forward twiddle k < 32, ws = psi^brv(k) centred
 template <class P>
 struct FwdSignedTw {
@@ -427,27 +463,12 @@ struct FwdSignedTw {
     constexpr FwdSignedTw() : wn(), wp()
     {
         for (uint32_t k = 0; k < 32; k++) {
-            const TwPair c = csigned_tw(cpow(P::PSI, cbrv32(k, P::LOGN), P::Q), P::Q);
+            const TwPair c = csigned_tw(cpow(P::PSI, brv_bits(k, P::LOGN), P::Q), P::Q);
             wn[k] = 0u - c.x;
             wp[k] = c.y;
         }
     }
 };
-
-// CT butterfly with typed operands: XS / YS = x / y in S form, YOS = leave
-// y' in S form (no +2q); RED = reduce x (off for canonical inputs).  y in S
-// form takes the signed Shoup quotient (centred twiddle (wsn, wps)).
-template <uint32_t Q, bool RED, bool XS, bool YS, bool YOS>
-__device__ __forceinline__ void ct_bfly_t(uint32_t &x, uint32_t &y, uint32_t wn, uint32_t wp)
-{
-    const uint32_t a = !RED ? x : XS ? umin(x, x + 2 * Q) : csub<2 * Q>(x);   // [0, 2q)
-    uint32_t qe;
-    if constexpr (YS) qe = (uint32_t)(((int64_t)(int32_t)y * (int32_t)wp - 0x80000000ll) >> 32);
-    else qe = __umulhi(y, wp);
-    const uint32_t tn = madlo32(qe, Q, y * wn);   // -t, t in [0, 2q)
-    x = a - tn;
-    y = YOS ? a + tn : a + tn + 2 * Q;
-}
 
 template <class P>
 __device__ __forceinline__ void fwd_pass1_lz(uint32_t (&r)[32], uint32_t h, const uint2 *tw, const uint2 *sw)
@@ -668,6 +689,8 @@ struct BaseMul {
         }
     }
 
+    // The callers' entry.  It only forwards, but calling run_zsplit directly
+    // changes k_poly_mul<*, false> and k_poly_mul_large<4, false>.
     template <bool ODD_S = false>
     static __device__ __forceinline__ void run(uint32_t (&ra)[32], const uint32_t (&rb)[32], const uint2 *tab, uint32_t lane)
     {
@@ -708,12 +731,32 @@ __device__ __forceinline__ void inv_pass1_head(uint32_t (&r)[32], uint32_t h, co
     }
 }
 
-// The last GS stage (pos bit LOGN-1, j bits 4): x' = (x+y) s0, y' = (x-y) s1
-// with s0 = (s0w, s0p) a Shoup pair and s1 = (s1w, s1p) a centred signed
-// pair (the stage's twiddle times the scaling), outputs in [0,2q), canonical
-// when CANON.  `emit(j, v)` is called with each final output as soon as it is
-// computed (the kernels store from there, so the 32 stores interleave with
-// the last stage instead of queueing behind it as one tail).
+// The last GS butterfly of every inverse (the stage on pos bit LOGN-1, k = 1)
+// with the scaling folded in: x' = (x + y) S0 by a Shoup product (x + y in
+// [0,4q)), y' = (x - y) S1 by a signed one (S1 = S0 psi^-brv(1), centred;
+// x - y in (-2q, 2q) as a signed value), both in [0,2q).  Two calls, the sum
+// first: one helper that returns both halves reorders the products.
+template <class P, uint32_t S0>
+__device__ __forceinline__ uint32_t gs_last_sum(uint32_t x, uint32_t y)
+{
+    constexpr uint32_t S0P = cshoup(S0, P::Q);
+    return shoup_mul<P::Q>(x + y, S0, S0P);
+}
+template <class P, uint32_t S1>
+__device__ __forceinline__ uint32_t gs_last_diff(uint32_t x, uint32_t y)
+{
+    constexpr TwPair S1S = csigned_tw(S1, P::Q);
+    return sshoup_mul<P::Q>(x - y, S1S.x, S1S.y);
+}
+
+// The last GS stage of a 32-register unit (j bit 4) with its constants as
+// values, s0 = (s0w, s0p) a Shoup pair and s1 = (s1w, s1p) a centred signed
+// pair (the large-n sub-trees read s1 from a table); outputs in [0,2q),
+// canonical when CANON.  `emit(j, v)` is called with each final output as soon
+// as it is computed (the kernels store from there, so the 32 stores interleave
+// with the last stage instead of queueing behind it as one tail).  Both
+// operands are formed before either product: written with gs_last_sum /
+// gs_last_diff the p-III kernels come out in another order.
 template <class P, bool CANON, class Emit = NoEmit>
 __device__ __forceinline__ void inv_last_stage(uint32_t (&r)[32], uint32_t s0w, uint32_t s0p, uint32_t s1w, uint32_t s1p,
                                                const Emit &emit = Emit())
@@ -731,6 +774,14 @@ __device__ __forceinline__ void inv_last_stage(uint32_t (&r)[32], uint32_t s0w, 
         emit(j + 16, r[j + 16]);
     }
 }
+// the same from the constants S0, S1 themselves
+template <class P, bool CANON, uint32_t S0, uint32_t S1, class Emit = NoEmit>
+__device__ __forceinline__ void inv_last_scaled(uint32_t (&r)[32], const Emit &emit = Emit())
+{
+    constexpr uint32_t S0P = cshoup(S0, P::Q);
+    constexpr TwPair S1S = csigned_tw(S1, P::Q);
+    inv_last_stage<P, CANON>(r, S0, S0P, S1S.x, S1S.y, emit);
+}
 
 // inverse pass 1: the head, then the last stage with the n^-1 scaling (times
 // the S0 / S1 constants), output canonical.
@@ -738,9 +789,7 @@ template <int PS, class P, uint32_t S0, uint32_t S1, class Emit = NoEmit>
 __device__ __forceinline__ void inv_pass1(uint32_t (&r)[32], uint32_t h, const uint2 *sw, const Emit &emit = Emit())
 {
     inv_pass1_head<P>(r, h, tw_base<PS, true>(), sw);
-    constexpr uint32_t S0P = cshoup(S0, P::Q);
-    constexpr TwPair S1S = csigned_tw(S1, P::Q);
-    inv_last_stage<P, true>(r, S0, S0P, S1S.x, S1S.y, emit);
+    inv_last_scaled<P, true, S0, S1>(r, emit);
 }
 
 // ------------------------------------------------------------------------
@@ -772,11 +821,19 @@ __device__ __forceinline__ void load32(uint32_t (&r)[32], const uint32_t *src, O
 // The first unit's global loads are issued before the workgroup prologue
 // (`prologue` = the LDS twiddle-table fill + barrier), so the fill latency
 // hides under the first unit's HBM latency.
-template <int WAVES, class Prologue, class Load, class Process>
+// NR: registers per lane (n = 4096 / 8192, one wave per polynomial: 64 / 128;
+// those kernels' `load` / `process` lambdas are always_inline: the n = 8192
+// bodies are too large for the inliner's heuristics, and an outlined body
+// takes the register array by reference, in scratch memory).
+// The fused products (k_poly_mul, k_poly_mul_k, ntt_mulkl_body.hpp) walk the
+// same chunk with a hand-written `for (it < ppw; u += WAVES)` loop: as a
+// helper taking the body as a closure the same instructions come out in
+// another order, so those three stay written out.
+template <int WAVES, int NR = 32, class Prologue, class Load, class Process>
 __device__ __forceinline__ void chunk_loop(uint32_t nunits, uint32_t ppw, Prologue &prologue, Load &load,
                                            Process &process)
 {
-    uint32_t r[32];
+    uint32_t r[NR];
     uint32_t u = blockIdx.x * (WAVES * ppw) + wave_id();
     if (u < nunits) load(r, u);
     prologue();   // every wave reaches the barrier inside
@@ -823,15 +880,13 @@ constexpr int MUL_LOGR = 3;
 // both directions instead of 31.5) and runs as two 8-wave workgroups per CU
 // (same 4 waves/SIMD): the CU no longer drains to start the next workgroup.
 // p-III 7.69 -> 7.35 ms, p-I 3.46 -> 3.25 ms per 2^20 (profiles/r04/r/)
-template <int PS, bool BHAT> constexpr bool mul_compact() { return !BHAT; }
-template <int PS, bool BHAT = false> constexpr int mul_wg() { return mul_compact<PS, BHAT>() ? 512 : MUL_WG; }
-template <int PS> constexpr int mul_occ() { return MUL_WAVES_PER_SIMD; }
+template <bool BHAT> constexpr bool mul_compact() { return !BHAT; }
+template <bool BHAT = false> constexpr int mul_wg() { return mul_compact<BHAT>() ? 512 : MUL_WG; }
 // lane-table entries a compact table keeps: the stages on pos bits 4 .. LOGR
 // read entries 0 .. 2^(5-LOGR) - 2, BaseMul's zeta the last 2^(4-LOGR) of them
 constexpr int MUL_CENT = (1 << (5 - MUL_LOGR)) - 1;
 // compact table image: entries 0..MUL_CENT-1 (L lanes each), then the 32 bit-5 pairs
 template <class P> constexpr int mul_ctab_words() { return MUL_CENT * (int)tw2_lanes<P>() * 2 + 64; }
-template <int PS> constexpr int mul_logr() { return MUL_LOGR; }
 constexpr int WG = 256;   // elementwise kernels
 constexpr int NTT_WAVES = NTT_WG / 64;
 constexpr int NTT_LDS_WORDS = NTT_WAVES * XPOSE_WORDS + TW2_WORDS;
@@ -870,21 +925,12 @@ __global__ __launch_bounds__(NTT_WG, NTT_WAVES_PER_SIMD) void k_ntt_fwd(const ui
             }
         }
     };
-    auto front = [&](uint32_t (&r)[32], uint32_t) {
+    auto process = [&](uint32_t (&r)[32], uint32_t u) {
         fwd_pass1<PS, P>(r, L.h, tw2 + TW2_ENTRIES * 64 + opaque_zero());
         lds_p1_to_p2<P>(r, buf, L);
-        if constexpr (BR) {
-            fwd_pass2<P>(r, tw2 + opaque_zero(), L.lane);
-            lds_p2_to_p1<P>(r, buf, L);
-        }
-    };
-    auto back = [&](uint32_t (&r)[32], uint32_t u) {
-        if constexpr (!BR) fwd_pass2<P>(r, tw2 + opaque_zero(), L.lane);
+        fwd_pass2<P>(r, tw2 + opaque_zero(), L.lane);
+        if constexpr (BR) lds_p2_to_p1<P>(r, buf, L);
         store(r, u);
-    };
-    auto process = [&](uint32_t (&r)[32], uint32_t u) {
-        front(r, u);
-        back(r, u);
     };
     chunk_loop<NTT_WAVES>(nunits, ppw, prologue, load, process);
 }
@@ -911,12 +957,10 @@ __global__ __launch_bounds__(NTT_WG, NTT_WAVES_PER_SIMD) void k_ntt_inv(const ui
         if constexpr (BR) src += LT::BIG ? 32 * L.h : 0u;   // brl + 32 h = l5 + 64 h (p1s_off)
         load32(r, src, [](int j) { return BR ? p1s_off<P>(j) : brv5(j) * LT::S; });
     };
-    auto front = [&](uint32_t (&r)[32], uint32_t) {
+    auto process = [&](uint32_t (&r)[32], uint32_t u) {
         if constexpr (BR) lds_p1_to_p2<P>(r, buf, L);
         inv_pass2<P>(r, tw2 + opaque_zero(), L.lane);
         lds_p2_to_p1<P>(r, buf, L);
-    };
-    auto back = [&](uint32_t (&r)[32], uint32_t u) {
         const uint32_t poly = L.poly(u);
         uint32_t *dst = out + LT::unit_base(u) + L.col();   // pass-1 layout: natural lane index
         const bool valid = LT::BIG || poly < npoly;
@@ -924,10 +968,6 @@ __global__ __launch_bounds__(NTT_WG, NTT_WAVES_PER_SIMD) void k_ntt_inv(const ui
             if (valid) st_out(dst + LT::S * j, v);
         };
         inv_pass1<PS, P, P::NINV, P::C1>(r, L.h, tw2 + TW2_ENTRIES * 64 + opaque_zero(), emit);
-    };
-    auto process = [&](uint32_t (&r)[32], uint32_t u) {
-        front(r, u);
-        back(r, u);
     };
     chunk_loop<NTT_WAVES>(nunits, ppw, prologue, load, process);
 }
@@ -987,13 +1027,13 @@ __device__ __forceinline__ void fill_tw2_compact(uint2 *tab)
 }
 
 template <int PS, bool BHAT, int VAR = 0>
-__global__ __launch_bounds__((mul_wg<PS, BHAT>()), mul_occ<PS>()) void k_poly_mul(const uint32_t *a, const uint32_t *b, uint32_t *c, uint32_t npoly, uint32_t ppw)
+__global__ __launch_bounds__((mul_wg<BHAT>()), MUL_WAVES_PER_SIMD) void k_poly_mul(const uint32_t *a, const uint32_t *b, uint32_t *c, uint32_t npoly, uint32_t ppw)
 {
     using P = typename PSel<PS>::T;
     using LT = Lane<P>;
-    constexpr bool CMP = mul_compact<PS, BHAT>();
-    static_assert(MUL_CENT >= (1 << (5 - mul_logr<PS>())) - 1, "the compact table holds every lane entry pass 2 reads");
-    constexpr int WG_ = mul_wg<PS, BHAT>();
+    constexpr bool CMP = mul_compact<BHAT>();
+    static_assert(MUL_CENT >= (1 << (5 - MUL_LOGR)) - 1, "the compact table holds every lane entry pass 2 reads");
+    constexpr int WG_ = mul_wg<BHAT>();
     constexpr int WAVES = WG_ / 64;
     constexpr int TABW = CMP ? mul_ctab_words<P>() : TW2_WORDS;   // words per direction
     constexpr int SWO = CMP ? MUL_CENT * (int)tw2_lanes<P>() : TW2_ENTRIES * 64;   // bit-5 pairs' offset (pairs)
@@ -1041,8 +1081,8 @@ __global__ __launch_bounds__((mul_wg<PS, BHAT>()), mul_occ<PS>()) void k_poly_mu
                 if (valid) st_out(pc + LT::S * j, ra[j] + rb[j]);
             continue;
         }
-        constexpr bool LZ = !BHAT;   // typed forwards (fwd_pass1_lz)
-        if constexpr (LZ) fwd_pass1_lz<P>(ra, L.h, tw_base<PS, false>(), ftw2 + SWO + opaque_zero());
+        // poly_mul: typed forwards (fwd_pass1_lz / fwd_pass2_lz)
+        if constexpr (!BHAT) fwd_pass1_lz<P>(ra, L.h, tw_base<PS, false>(), ftw2 + SWO + opaque_zero());
         else fwd_pass1<PS, P>(ra, L.h, ftw2 + SWO + opaque_zero());
         // loop-invariant transpose addresses (poly_mul: affordable once the
         // typed forwards took the p-III kernel from 126 to 96 VGPRs, 121 with
@@ -1051,8 +1091,8 @@ __global__ __launch_bounds__((mul_wg<PS, BHAT>()), mul_occ<PS>()) void k_poly_mu
         // twiddle table; hoisted: 22 spilled VGPRs)
         constexpr bool HOIST = BHAT ? P::LOGN == 11 : true;
         lds_p1_to_p2<P>(ra, buf, HOIST ? L : LT(opaque_lane()));
-        if constexpr (LZ) fwd_pass2_lz<P, mul_logr<PS>()>(ra, ftw2 + opaque_zero(), L.lane);
-        else fwd_pass2<P, BHAT ? 0 : mul_logr<PS>()>(ra, ftw2 + opaque_zero(), L.lane);
+        if constexpr (!BHAT) fwd_pass2_lz<P, MUL_LOGR>(ra, ftw2 + opaque_zero(), L.lane);
+        else fwd_pass2<P>(ra, ftw2 + opaque_zero(), L.lane);
         // b-hat is in natural order: register j of the pass-2 layout holds
         // index brv5(j)*S + lane (the forward's store mapping)
         if constexpr (VAR == 2) {
@@ -1070,15 +1110,14 @@ __global__ __launch_bounds__((mul_wg<PS, BHAT>()), mul_occ<PS>()) void k_poly_mu
             // incomplete domain: both forwards stop above pos bit LOGR-1,
             // products mod x^(2^LOGR) -+ zeta, the inverse starts at pos bit
             // LOGR (BaseMul)
-            if constexpr (LZ) fwd_pass1_lz<P>(rb, L.h, tw_base<PS, false>(), ftw2 + SWO + opaque_zero());
-            else fwd_pass1<PS, P>(rb, L.h, ftw2 + SWO + opaque_zero());
+            using BM = BaseMul<P, MUL_LOGR>;
+            fwd_pass1_lz<P>(rb, L.h, tw_base<PS, false>(), ftw2 + SWO + opaque_zero());
             lds_p1_to_p2<P>(rb, buf, L);
-            if constexpr (LZ) fwd_pass2_lz<P, mul_logr<PS>()>(rb, ftw2 + opaque_zero(), L.lane);
-            else fwd_pass2<P, mul_logr<PS>()>(rb, ftw2 + opaque_zero(), L.lane);
-            BaseMul<P, mul_logr<PS>()>::template run<LZ>(ra, rb, ftw2 + opaque_zero(), L.lane);
-            inv_pass2<P, mul_logr<PS>(), BaseMul<P, mul_logr<PS>()>::WIDE>(ra, itw2 + opaque_zero(), L.lane);
+            fwd_pass2_lz<P, MUL_LOGR>(rb, ftw2 + opaque_zero(), L.lane);
+            BM::template run<true>(ra, rb, ftw2 + opaque_zero(), L.lane);   // the typed forwards leave the odd residues S
+            inv_pass2<P, MUL_LOGR, BM::WIDE>(ra, itw2 + opaque_zero(), L.lane);
             lds_p2_to_p1<P>(ra, buf, L);
-            inv_pass1<PS, P, P::template ninv_r<mul_logr<PS>()>(), P::template c1_r<mul_logr<PS>()>()>(ra, L.h, itw2 + SWO + opaque_zero(), emit);
+            inv_pass1<PS, P, P::template ninv_r<MUL_LOGR>(), P::template c1_r<MUL_LOGR>()>(ra, L.h, itw2 + SWO + opaque_zero(), emit);
         } else {
 #pragma unroll
             for (int j = 0; j < 32; ++j) ra[j] = mont_mul<P>(csub<P::Q2>(ra[j]), csub<P::Q2>(rb[j]));   // b-hat < 2q

@@ -340,7 +340,7 @@ template <int PS> struct LMul {
                 const LaunchShape l = large_shape(batch, LG::SLOTS, d);
                 hipLaunchKernelGGL((k_poly_mul_large<PS, BHAT>), dim3(l.grid), dim3(LG::NT), 0, s, a, b, c, nb, l.chunk);
             } else {
-                constexpr int wg = mul_wg<PS, BHAT>();
+                constexpr int wg = mul_wg<BHAT>();
                 const LaunchShape l = batch_shape<PS>(batch, wg / 64, d);
                 hipLaunchKernelGGL((k_poly_mul<PS, BHAT>), dim3(l.grid), dim3(wg), 0, s, a, b, c, nb, l.chunk);
             }

@@ -500,8 +500,8 @@ void k_poly_mul_large(const uint32_t *a, const uint32_t *b, uint32_t *c, uint32_
         // through b's transform)
         load32(ra, a + base + opaque_lane(), [](int j) { return large_off<LG>(j); });
         if (PF) load32(rb, b + bbase + opaque_lane(), boff);
-        constexpr int LOGR = LG::INC ? mul_logr<2>() : 0;
-        using BM = BaseMul<P, mul_logr<2>()>;
+        constexpr int LOGR = LG::INC ? MUL_LOGR : 0;
+        using BM = BaseMul<P, MUL_LOGR>;
         w.template fwd<LOGR>(ra);
 #pragma unroll
         for (int j = 0; j < 32; ++j) asm volatile("" : "+v"(ra[j]));   // phase boundary (register pressure)

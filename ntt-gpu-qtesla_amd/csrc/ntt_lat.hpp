@@ -118,9 +118,7 @@ __device__ uint2 g_lattw4[2][8192];
 template <int PS, bool INV>
 __device__ __forceinline__ const uint2 *lat_tw()
 {
-    if constexpr (PS == 0) return INV ? c_inv0 : c_fwd0;
-    else if constexpr (PS == 1) return INV ? c_inv1 : c_fwd1;
-    else if constexpr (PS == 2) return INV ? c_inv2 : c_fwd2;
+    if constexpr (PS <= 2) return tw_table<PS, INV>();
     else if constexpr (PS == 3) return g_lattw3[INV ? 1 : 0];
     else return g_lattw4[INV ? 1 : 0];
 }
@@ -154,13 +152,6 @@ struct LatGeo {
         return base(j, g) + ((uint32_t)(e >> 1) << gh(j)) + ((uint32_t)(e & 1) << gl(j));
     }
 };
-
-__host__ __device__ constexpr uint32_t lat_brv(uint32_t x, int bits)
-{
-    uint32_t r = 0;
-    for (int i = 0; i < bits; ++i) r |= ((x >> i) & 1u) << (bits - 1 - i);
-    return r;
-}
 
 // Every pass's twiddles of one direction for group g (3 per radix-4 pass, 2
 // for the lone stage), loaded up front so that their latency overlaps the
@@ -270,16 +261,14 @@ __device__ __forceinline__ void lat_inv(uint32_t (&v)[LatGeo<PSel<PS>::T::LOGN>:
             lat_xchg<G, NB>(v, lds, t, x0 + NP - j, [&](uint32_t g, int e) { return G::pos(j, g, e); },
                             [&](uint32_t g, int e) { return G::pos(j - 1, g, e); });
     });
-    // stage L-1 (k = 1) with the scaling folded in (inv_last_stage)
-    constexpr uint32_t S0P = cshoup(S0, P::Q);
-    constexpr TwPair S1S = csigned_tw(S1, P::Q);
+    // stage L-1 (k = 1) with the scaling folded in (gs_last_sum / gs_last_diff)
 #pragma unroll
     for (int r = 0; r < G::R; ++r)
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             const uint32_t x = v[r][e], y = v[r][e + 2];
-            v[r][e] = csub<P::Q>(shoup_mul<P::Q>(x + y, S0, S0P));
-            v[r][e + 2] = csub<P::Q>(sshoup_mul<P::Q>(x - y, S1S.x, S1S.y));
+            v[r][e] = csub<P::Q>(gs_last_sum<P, S0>(x, y));
+            v[r][e + 2] = csub<P::Q>(gs_last_diff<P, S1>(x, y));
         }
 }
 
@@ -331,7 +320,7 @@ __global__ __launch_bounds__(LatGeo<PSel<PS>::T::LOGN>::T) void k_ntt_lat(const 
 #pragma unroll
                 for (int e = 0; e < 4; ++e) st_out(dst + G::pos(NP - 1, t + (uint32_t)r * G::T, e), v[r][e]);
         } else {
-            lat_xchg<G, 1>(v, lds, t, NP - 1, [&](uint32_t g, int e) { return lat_brv(G::pos(NP - 1, g, e), L); },
+            lat_xchg<G, 1>(v, lds, t, NP - 1, [&](uint32_t g, int e) { return brv_bits(G::pos(NP - 1, g, e), L); },
                            [&](uint32_t g, int e) { return g + GN * e; });
 #pragma unroll
             for (int r = 0; r < R; ++r)
@@ -342,7 +331,7 @@ __global__ __launch_bounds__(LatGeo<PSel<PS>::T::LOGN>::T) void k_ntt_lat(const 
         // A[pos] = X[brv(pos)]: a natural-order input reaches the last forward
         // pass's groups through LDS (exchange 0)
         if constexpr (!BR)
-            lat_xchg<G, 1>(v, lds, t, 0, [&](uint32_t g, int e) { return lat_brv(g + GN * e, L); },
+            lat_xchg<G, 1>(v, lds, t, 0, [&](uint32_t g, int e) { return brv_bits(g + GN * e, L); },
                            [&](uint32_t g, int e) { return G::pos(NP - 1, g, e); });
         lat_inv<PS, 1, P::NINV, P::C1>(v, w, lds, t, 0);
 #pragma unroll
@@ -376,7 +365,7 @@ __global__ __launch_bounds__(LatGeo<PSel<PS>::T::LOGN>::T) void k_poly_mul_lat(c
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         v[0][e] = ld_in(a + off + t + GN * e);
-        if constexpr (BHAT) bh[e] = ld_in(b + off + lat_brv(G::pos(NP - 1, t, e), L));
+        if constexpr (BHAT) bh[e] = ld_in(b + off + brv_bits(G::pos(NP - 1, t, e), L));
         else v[NF - 1][e] = ld_in(b + off + t + GN * e);
     }
     LatTw<PS, false> fw[1];

@@ -266,13 +266,11 @@ __device__ __forceinline__ void latr_inv(uint32_t (&v)[1 << RB], LatRTw<PS, true
     });
     if constexpr (!ARITH) return;
     // stage L-1 (k = 1, group bit RB-1 of pass 0) with the scaling folded in
-    constexpr uint32_t S0P = cshoup(S0, P::Q);
-    constexpr TwPair S1S = csigned_tw(S1, P::Q);
 #pragma unroll
     for (int e = 0; e < NE / 2; ++e) {
         const uint32_t x = v[e], y = v[e + NE / 2];
-        v[e] = csub<P::Q>(shoup_mul<P::Q>(x + y, S0, S0P));
-        v[e + NE / 2] = csub<P::Q>(sshoup_mul<P::Q>(x - y, S1S.x, S1S.y));
+        v[e] = csub<P::Q>(gs_last_sum<P, S0>(x, y));
+        v[e + NE / 2] = csub<P::Q>(gs_last_diff<P, S1>(x, y));
     }
 }
 
@@ -330,7 +328,7 @@ __global__ __launch_bounds__((LatRGeo<PSel<PS>::T::LOGN, RB>::T)) void k_ntt_lat
             constexpr LatPad pd = latr_pad(L, RB, false, NP - 1);
             const uint32_t bt = __builtin_bitreverse32(t) >> (32 - (L - RB));
             latr_xchg<G>(v, lds, NP - 1, latr_phys(bt, pd),
-                         [&](int e) { return latr_phys(lat_brv(e, RB) << (L - RB), pd); }, latr_phys(t, pd),
+                         [&](int e) { return latr_phys(brv_bits(e, RB) << (L - RB), pd); }, latr_phys(t, pd),
                          [&](int e) { return latr_phys(T * e, pd); });
 #pragma unroll
             for (int e = 0; e < NE; ++e) store(dst + t + T * e, v[e]);
@@ -342,7 +340,7 @@ __global__ __launch_bounds__((LatRGeo<PSel<PS>::T::LOGN, RB>::T)) void k_ntt_lat
             // brv(t + T e) = brv_L(t) + brv_RB(e)
             constexpr LatPad pd = latr_pad(L, RB, true, NP - 1);
             const uint32_t bt = __builtin_bitreverse32(t) >> (32 - L);
-            latr_xchg<G>(v, lds, 0, latr_phys(bt, pd), [&](int e) { return latr_phys(lat_brv(e, RB), pd); },
+            latr_xchg<G>(v, lds, 0, latr_phys(bt, pd), [&](int e) { return latr_phys(brv_bits(e, RB), pd); },
                          latr_phys(NE * t, pd), [&](int e) { return latr_phys(e, pd); });
         }
         latr_inv<PS, RB, P::NINV, P::C1, ARITH>(v, W, lds, t, BR ? -1 : 0);

@@ -126,9 +126,7 @@ __global__ __launch_bounds__(MULK_WG, MULK_WAVES_PER_SIMD) void k_poly_mul_k(con
                 if (valid) st_out(po + LT::S * j, v);
             };
             inv_pass1_head<P>(r, L.h, tw_base<PS, true>(), itw2 + SWO + opaque_zero());
-            constexpr uint32_t S0P = cshoup(P::NINV_R, P::Q);
-            constexpr TwPair S1S = csigned_tw(P::C1_R, P::Q);
-            inv_last_stage<P, !ADD>(r, P::NINV_R, S0P, S1S.x, S1S.y, emit);
+            inv_last_scaled<P, !ADD, P::NINV_R, P::C1_R>(r, emit);
         }
     }
 }

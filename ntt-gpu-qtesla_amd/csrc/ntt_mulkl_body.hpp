@@ -96,9 +96,7 @@
                 }
             };
             inv_pass1_head<P>(r, Ln.h, tw_base<PS, true>(), itw2 + SWO + opaque_zero());
-            constexpr uint32_t S0P = cshoup(P::NINV_R, P::Q);
-            constexpr TwPair S1S = csigned_tw(P::C1_R, P::Q);
-            inv_last_stage<P, !ADD>(r, P::NINV_R, S0P, S1S.x, S1S.y, emit);
+            inv_last_scaled<P, !ADD, P::NINV_R, P::C1_R>(r, emit);
             if constexpr (RND) {
                 // bytes [16 pl, 16 pl + 16) of each half of the polynomial; hi
                 // is addressed like out, a byte per word

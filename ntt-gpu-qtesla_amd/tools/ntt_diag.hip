@@ -118,33 +118,25 @@ __global__ __launch_bounds__(Big<PS>::NT, Big<PS>::OCC) void k_big_mem(const uin
             const uint32_t wb = big_wbase(opaque_lane());
             const Lane<P> LB(opaque_lane());
             if constexpr (!INV) {   // A'' rows -> b128 reads of layout B -> B-order stores
-                sfor<32>([&](auto T) { buf[big_waddr(wb, T)] = r[BG::creg(C, T)]; });
+                big_rows_wr<BG, C>(r, buf, wb);
                 compiler_fence();
                 uint32_t v[32];
-                sfor<8>([&](auto Q) {
-                    const uint4 x = *reinterpret_cast<const uint4 *>(buf + LB.rbase + ((4u * Q) ^ LB.rxm));
-                    v[4 * Q + 0] = x.x;
-                    v[4 * Q + 1] = x.y;
-                    v[4 * Q + 2] = x.z;
-                    v[4 * Q + 3] = x.w;
-                });
+                xpose_rd128(v, buf, LB);
                 compiler_fence();
                 sfor<32>([&](auto JP) { st_out(dst + BG::boff(C, JP), v[JP]); });
             } else {   // layout B -> b128 writes -> A'' rows back into the registers
-                sfor<8>([&](auto Q) {
-                    *reinterpret_cast<uint4 *>(buf + LB.rbase + ((4u * Q) ^ LB.rxm)) =
-                        make_uint4(r[BG::creg(C, 4 * Q + 0)], r[BG::creg(C, 4 * Q + 1)], r[BG::creg(C, 4 * Q + 2)],
-                                   r[BG::creg(C, 4 * Q + 3)]);
-                });
+                uint32_t v[32];
+                sfor<32>([&](auto JP) { v[JP] = r[BG::creg(C, JP)]; });
+                xpose_wr128(v, buf, LB);
                 compiler_fence();
-                sfor<32>([&](auto T) { r[BG::creg(C, T)] = buf[big_waddr(wb, T)]; });
+                big_rows_rd<BG, C>(r, buf, wb);
                 compiler_fence();
             }
         });
         if constexpr (INV)   // layout A stores (lane-contiguous 256-B runs)
             sfor<BG::R>([&](auto J) { st_out(dst + 64u * (uint32_t)J, r[J]); });
     };
-    big_loop<BG>(npoly, ppw, prologue, load, process);
+    chunk_loop<BG::WAVES, BG::R>(npoly, ppw, prologue, load, process);
 }
 
 template <int W>
@@ -196,10 +188,10 @@ int launch(int op, int variant, uint32_t *out, const uint32_t *in, uint32_t nb, 
     case 49:
     case 50: {
         // the library's poly_mul launch shape (launch_for(OP_MUL)): 4 workgroups per CU
-        constexpr int W = mul_wg<PS>() / 64;
+        constexpr int W = mul_wg() / 64;
         uint32_t mp = units / (W * 4 * g_cus);
         mp = mp < 1 ? 1 : (mp > 16 ? 16 : mp);
-        const dim3 gm((units + W * mp - 1) / (W * mp)), bm(mul_wg<PS>());
+        const dim3 gm((units + W * mp - 1) / (W * mp)), bm(mul_wg());
         if (variant == 0) hipLaunchKernelGGL((k_poly_mul<PS, false, 0>), gm, bm, 0, s, in, in, out, nb, mp);
         else if (variant == 1) hipLaunchKernelGGL((k_poly_mul<PS, false, 1>), gm, bm, 0, s, in, in, out, nb, mp);
         else hipLaunchKernelGGL((k_poly_mul<PS, false, 2>), gm, bm, 0, s, in, in, out, nb, mp);

@@ -249,13 +249,11 @@ __device__ __forceinline__ void wg_inv(uint32_t (&v)[4], uint32_t *lds, uint32_t
         gs_bfly<P::Q>(v[0], v[1], t2.x, t2.y);
         gs_bfly<P::Q>(v[2], v[3], t3.x, t3.y);
     }
-    constexpr uint32_t S0P = cshoup(P::NINV, P::Q);
-    constexpr TwPair S1S = csigned_tw(P::C1, P::Q);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const uint32_t x = v[j], y = v[j + 2];
-        v[j] = csub<P::Q>(shoup_mul<P::Q>(x + y, P::NINV, S0P));
-        v[j + 2] = csub<P::Q>(sshoup_mul<P::Q>(x - y, S1S.x, S1S.y));
+        v[j] = csub<P::Q>(gs_last_sum<P, P::NINV>(x, y));
+        v[j + 2] = csub<P::Q>(gs_last_diff<P, P::C1>(x, y));
     }
 }
 
