@@ -303,6 +303,52 @@ int ntt_xof(uint8_t *d_out, size_t outlen, const uint8_t *d_in0, size_t len0,
 int poly_challenge(uint32_t *d_pos, uint32_t *d_val, const uint8_t *d_seed,
                    size_t seedlen, size_t batch, int h, int param_set, void *stream);
 
+/* qTESLA's masking polynomial: one seed and a nonce to the n coefficients of
+ * y, canonical in [0, q), centred in [-B, B] with B = 2^(bits-1) - 1 -- the
+ * signer's first step, so that v = a y, [v]_M, H, Enc(c') and z = y + s c all
+ * start from device memory.
+ *   d_y     [batch][n] uint32, every word written
+ *   d_seed  [batch][seedlen] bytes
+ *   d_nonce NULL, or [batch] uint32: one attempt counter per message, so that
+ *           a batch whose messages are at different attempts is one launch
+ * Message b uses nonce_b = ((d_nonce ? d_nonce[b] : 0) + nonce) & 0xFF.
+ * `bits` is qTESLA's B_BITS + 1 (20 for p-I, 22 for p-III) and the hash is the
+ * caller's (the library keeps no scheme constants); n and q are param_set's.
+ * Each seed on its own, with rate = 168 / 136 and ntt_xof's cshake*_simple
+ * (sample_y of qTESLA round 2, restated from memory -- a first call of 3 n
+ * bytes, then single-rate-block refills with the customisation counted up,
+ * and the (nonce << 8) domain separation; this statement, not the upstream
+ * file, is what the tests bind):
+ *   mask = 2^bits - 1;  B = 2^(bits-1) - 1;  cstm = (nonce_b << 8) & 0xFFFF
+ *   buf = cshake_simple(algo, seed, outlen = 3 n, cstm);  limit = 3 n;  pos = 0;  r = 0;  i = 0
+ *   while i < n:
+ *       if pos >= limit:
+ *           r += 1;  buf = cshake_simple(algo, seed, outlen = rate, (cstm + r) & 0xFFFF)
+ *           limit = 3 * (rate / 3);  pos = 0         (56 draws; 45 draws, byte 135 unused)
+ *       v = (buf[pos] | buf[pos+1] << 8 | buf[pos+2] << 16) & mask;  pos += 3
+ *       if v != mask:  y[i] = (v - B) mod q;  i += 1      (v == mask would be 2^(bits-1))
+ * A draw is always three bytes; bits below 17 is outside qTESLA but legal.
+ * Refills are bounded, r <= NTT_SAMPLE_Y_REFILLS_MAX (no unbounded loop on the
+ * device, and cstm + r stays inside this nonce's range); with bits >= 2 a draw
+ * is accepted with probability >= 3/4 and 255 refills add >= 11 475 draws, so
+ * hash outputs never come near the bound.  Were it reached, the coefficients
+ * not yet drawn get 0.
+ * algo is NTT_XOF_SHAKE128 or NTT_XOF_SHAKE256.  All five parameter sets.
+ * Checks, in this order (the first defect decides):
+ *   NTT_ERR_PARAM  param_set; algo; bits outside 2 .. 24; nonce > 255; seedlen
+ *                  not a multiple of 8 or outside 8 .. rate - 8 (one absorb
+ *                  block: 160 / 128)
+ *   batch == 0     NTT_OK, nothing else is looked at
+ *   NTT_ERR_NULL   d_y, d_seed
+ *   NTT_ERR_ALIGN  d_y 16-byte, d_seed 8-byte, d_nonce 4-byte when not NULL
+ *   NTT_ERR_SIZE   batch > 2^31 - 1
+ *   NTT_ERR_ALIAS  d_y overlaps d_seed or d_nonce
+ * One seed per lane, as ntt_xof: the throughput comes from the batch. */
+#define NTT_SAMPLE_Y_REFILLS_MAX 255
+int poly_sample_y(uint32_t *d_y, const uint8_t *d_seed, size_t seedlen,
+                  const uint32_t *d_nonce, uint32_t nonce, size_t batch,
+                  int bits, int algo, int param_set, void *stream);
+
 /* Nussbaumer negacyclic product (the paper's alternate algorithm): the
  * reference's single-polynomial CPU routine nussbaumer_fft (NTT.cu:167-277,
  * driver test_nussbaumer :1987-2005), batched on the GPU and extended from

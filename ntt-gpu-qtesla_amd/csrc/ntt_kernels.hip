@@ -22,6 +22,7 @@
 #include "ntt_mulk.hpp"
 #include "ntt_mulkl.hpp"
 #include "ntt_round.hpp"
+#include "ntt_sample.hpp"
 #include "ntt_xof.hpp"
 #include "ntt_internal.h"
 #include "params.hpp"
@@ -713,6 +714,37 @@ int poly_challenge(uint32_t *d_pos, uint32_t *d_val, const uint8_t *d_seed, size
     hipLaunchKernelGGL(k_challenge, dim3((uint32_t)ceil_div(batch, (size_t)CHALLENGE_WG)), dim3(CHALLENGE_WG),
                        (size_t)p->n / 32 * CHALLENGE_WG * 4, (hipStream_t)stream, d_pos, d_val, (const uint64_t *)d_seed,
                        (uint32_t)(seedlen / 8), (uint32_t)batch, (uint32_t)h, p->n, p->q, (uint32_t)NTT_CHALLENGE_BLOCKS_MAX);
+    return finish_launch();
+}
+
+int poly_sample_y(uint32_t *d_y, const uint8_t *d_seed, size_t seedlen, const uint32_t *d_nonce, uint32_t nonce, size_t batch,
+                  int bits, int algo, int ps, void *stream)
+{
+    const ParamSet *p = param_set(ps);
+    if (!p || (algo != NTT_XOF_SHAKE128 && algo != NTT_XOF_SHAKE256)) return NTT_ERR_PARAM;
+    const size_t rate = algo == NTT_XOF_SHAKE128 ? 8 * XOF_RATE128 : 8 * XOF_RATE256;
+    if (bits < 2 || bits > 24 || nonce > 255) return NTT_ERR_PARAM;
+    if ((seedlen & 7u) || seedlen < 8 || seedlen > rate - 8) return NTT_ERR_PARAM;   // one absorb block
+    if (batch == 0) return NTT_OK;
+    if (!d_y || !d_seed) return NTT_ERR_NULL;
+    if ((((uintptr_t)d_y) & 15u) || (((uintptr_t)d_seed) & 7u) || (((uintptr_t)d_nonce) & 3u)) return NTT_ERR_ALIGN;
+    if (batch > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
+    const size_t ybytes = batch * p->n * 4;
+    if (ranges_overlap(d_y, ybytes, d_seed, batch * seedlen) || (d_nonce && ranges_overlap(d_y, ybytes, d_nonce, batch * 4)))
+        return NTT_ERR_ALIAS;
+    int rc;
+    DevInfo *d = nullptr;
+    if ((rc = device_ready(&d)) != NTT_OK) return rc;
+    const dim3 grid((uint32_t)ceil_div(batch, (size_t)SAMPLE_WG)), wg(SAMPLE_WG);
+    const uint32_t sw = (uint32_t)(seedlen / 8);
+    if (algo == NTT_XOF_SHAKE128)
+        hipLaunchKernelGGL(k_sample_y<XOF_RATE128>, grid, wg, 0, (hipStream_t)stream, d_y,
+                           (const uint64_t *)d_seed, sw, d_nonce, nonce, (uint32_t)batch, p->n, p->q, (uint32_t)bits,
+                           (uint32_t)NTT_SAMPLE_Y_REFILLS_MAX);
+    else
+        hipLaunchKernelGGL(k_sample_y<XOF_RATE256>, grid, wg, 0, (hipStream_t)stream, d_y,
+                           (const uint64_t *)d_seed, sw, d_nonce, nonce, (uint32_t)batch, p->n, p->q, (uint32_t)bits,
+                           (uint32_t)NTT_SAMPLE_Y_REFILLS_MAX);
     return finish_launch();
 }
 

@@ -94,6 +94,7 @@ def lib():
                                             ctypes.c_int, ctypes.c_int, _vp]
         L.ntt_xof.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_challenge.argtypes = [_vp, _vp, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, _vp]
+        L.poly_sample_y.argtypes = [_vp, _vp, _sz, _vp, ctypes.c_uint32, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_mul_nussbaumer.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.ntt_fill_uniform.argtypes = [_vp, _sz, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, _vp]
         L.ntt_last_hip_error.restype = ctypes.c_int
@@ -572,6 +573,7 @@ def poly_mul_ntt_kl_round(ys, ahat, param_set, d: int, hi=None, norms=None, add=
 XOF_ALGOS = {"shake128": 0, "shake256": 1}   # NTT_XOF_SHAKE128, NTT_XOF_SHAKE256
 XOF_OUT_MAX = 512          # NTT_XOF_OUT_MAX
 CHALLENGE_H_MAX = 128      # NTT_CHALLENGE_H_MAX
+SAMPLE_Y_REFILLS_MAX = 255   # NTT_SAMPLE_Y_REFILLS_MAX
 
 
 def _byte_rows(name: str, t, batch: int) -> int:
@@ -640,6 +642,40 @@ def poly_challenge(pos, val, seed, param_set, stream=None):
     _run("poly_challenge", (pos, val, seed), stream,
          lambda s: fn(pos.data_ptr(), val.data_ptr(), seed.data_ptr(), seedlen, nb, h, _ps(param_set), s))
     return pos, val
+
+
+def poly_sample_y(y, seed, param_set, bits: int, algo="shake256", nonce: int = 0, nonces=None, stream=None):
+    """qTESLA's sample_y: seed [batch, seedlen] int8/uint8 (seedlen a multiple
+    of 8 within 8 .. 160 for SHAKE128, 8 .. 128 for SHAKE256) to the masking
+    polynomials y, int32 [batch, n] (or flat), canonical in [0, q) and centred
+    in [-B, B], B = 2^(bits-1) - 1 with 2 <= bits <= 24 (qTESLA: 20 for p-I,
+    22 for p-III).  Message b is drawn at nonce (nonces[b] + nonce) & 0xFF:
+    nonce a scalar 0 .. 255, nonces None or an int32 [batch] device tensor of
+    per-message attempt counters.  Returns y."""
+    nb = _batch(y, _n(param_set))
+    if y.dim() > 1 and y.shape[0] != nb:
+        raise ValueError(f"y: shape {tuple(y.shape)}, expected [{nb}, n] or flat")
+    if not 2 <= int(bits) <= 24:
+        raise ValueError(f"bits = {bits}, expected 2 .. 24")
+    if not 0 <= int(nonce) <= 255:
+        raise ValueError(f"nonce = {nonce}, expected 0 .. 255")
+    if isinstance(algo, str) and algo not in XOF_ALGOS:
+        raise ValueError(f"algo {algo!r}, expected one of {sorted(XOF_ALGOS)}")
+    a = XOF_ALGOS[algo] if isinstance(algo, str) else int(algo)
+    seedlen = _byte_rows("seed", seed, nb)
+    smax = 128 if a == XOF_ALGOS["shake256"] else 160
+    if seed.dim() != 2 or not 8 <= seedlen <= smax:
+        raise ValueError(f"seed: shape {tuple(seed.shape)}, expected [{nb}, 8 .. {smax}]")
+    tensors = (y, seed)
+    pn = None
+    if nonces is not None:
+        if _batch(nonces, 1) != nb or nonces.dim() != 1:
+            raise ValueError(f"nonces: shape {tuple(nonces.shape)}, expected [{nb}]")
+        tensors, pn = (y, seed, nonces), nonces.data_ptr()
+    fn = lib().poly_sample_y
+    _run("poly_sample_y", tensors, stream,
+         lambda s: fn(y.data_ptr(), seed.data_ptr(), seedlen, pn, int(nonce), nb, int(bits), a, _ps(param_set), s))
+    return y
 
 
 def poly_mul_nussbaumer(c, a, b, param_set, ring="q", stream=None):
