@@ -349,6 +349,65 @@ int poly_sample_y(uint32_t *d_y, const uint8_t *d_seed, size_t seedlen,
                   const uint32_t *d_nonce, uint32_t nonce, size_t batch,
                   int bits, int algo, int param_set, void *stream);
 
+/* qTESLA's wire formats: coefficients to bit-packed rows and back -- a
+ * signature's z as n fields of B_BITS + 1 bits (p-I: 20, p-III: 22), a public
+ * key's t as k n fields of ceil(log2 q) bits (29 / 30) -- so that signature
+ * and key bytes go to and come from the device as they are on the wire.  Both
+ * calls are general in the field width, in signed or unsigned fields and in k
+ * polynomials per row; the library keeps no scheme constants.  (encode_sig /
+ * decode_sig / encode_pk / decode_pk of qTESLA round 2, bit layout restated
+ * from memory; this statement, not the upstream file, is what the tests bind.)
+ * Let q and n be param_set's, qbits the bit length of q (24 for ref, 29 for
+ * p-I, 30 for p-III and the larger sets) and b = bits.
+ *   Bit stream.  A polynomial's packed form is n b / 8 bytes.  Field i
+ *     occupies stream bits [i b, (i+1) b); stream bit j is bit j mod 8 of byte
+ *     j / 8, equivalently bit j mod 32 of little-endian dword j / 32.  For
+ *     b = 20 this is qTESLA's pt[0] = (z0 & m) | (z1 << 20),
+ *     pt[1] = (z1 >> 12) | (z2 << 8) | (z3 << 28), and so on.  n is a multiple
+ *     of 1024, so a polynomial is a multiple of 128 bytes.
+ *   Rows.  Row r of the byte side starts at r * stride and holds k
+ *     polynomials back to back, k n b / 8 bytes.  Bytes [k n b / 8, stride) of
+ *     a row belong to the caller (c', seed_a): poly_pack never writes them,
+ *     poly_unpack never reads them.  The coefficient side is dense
+ *     [batch][k][n] uint32.
+ *   poly_pack.  An input word x is < 2q, as for poly_round; x' = x mod q.
+ *     sgn = 1:  c = x' - q if x' > (q-1)/2, else x'; the field is c mod 2^b,
+ *               the two's-complement low b bits.
+ *     sgn = 0:  the field is x' mod 2^b.
+ *     A value outside the field's range is truncated: keeping values in range
+ *     is the caller's responsibility (a signer packs only a z that has passed
+ *     its norm test).
+ *   poly_unpack.  Let f be the field.
+ *     sgn = 1:  s is the sign extension of f; the output is s if s >= 0, else
+ *               s + q; the maximum is max |s| over the polynomial, so a field
+ *               of -2^(b-1) reports 2^(b-1).
+ *     sgn = 0:  the output is f if f < q, else f - q (always canonical:
+ *               b <= qbits gives f < 2q); the maximum is max f, the raw field,
+ *               so the caller sees a malformed key as a maximum >= q.
+ *     d_max is NULL or [batch][k] uint32; with it, decoding and the verifier's
+ *     max |z| test read the signature once.
+ *   Limits.  8 <= bits <= qbits - 1 when signed, 8 <= bits <= qbits when
+ *     unsigned; 1 <= k <= NTT_MUL_K_MAX; stride a multiple of 16 and
+ *     >= k n bits / 8.  With the signed limit 2^(b-1) <= (q-1)/2, hence
+ *       poly_pack(poly_unpack(bytes)) == bytes   for every byte string, and
+ *       poly_unpack(poly_pack(w)) == w mod q     whenever w's centred values
+ *                                                fit b bits;
+ *     unsigned, the byte round trip holds exactly when every f < q.
+ * All five parameter sets; asynchronous on `stream`; every output word is
+ * written once by a plain vector store.  Checks, in this order (the first
+ * defect decides):
+ *   NTT_ERR_PARAM  param_set; k; sgn not 0 or 1; bits; stride
+ *   batch == 0     NTT_OK, nothing else is looked at
+ *   NTT_ERR_NULL   d_out / d_w / d_in (d_max may be NULL)
+ *   NTT_ERR_ALIGN  byte side and coefficient side 16-byte, d_max 4-byte
+ *   NTT_ERR_SIZE   batch * k > 2^31 - 1
+ *   NTT_ERR_ALIAS  an output overlaps the input, or d_max overlaps d_w; the
+ *                  byte side's extent is (batch - 1) * stride + k n bits / 8 */
+int poly_pack(uint8_t *d_out, size_t stride, const uint32_t *d_w, size_t batch,
+              int k, int bits, int sgn, int param_set, void *stream);
+int poly_unpack(uint32_t *d_w, uint32_t *d_max /* [batch][k] or NULL */, const uint8_t *d_in,
+                size_t stride, size_t batch, int k, int bits, int sgn, int param_set, void *stream);
+
 /* Nussbaumer negacyclic product (the paper's alternate algorithm): the
  * reference's single-polynomial CPU routine nussbaumer_fft (NTT.cu:167-277,
  * driver test_nussbaumer :1987-2005), batched on the GPU and extended from

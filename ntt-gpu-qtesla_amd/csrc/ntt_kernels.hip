@@ -21,6 +21,7 @@
 #include "ntt_latr.hpp"
 #include "ntt_mulk.hpp"
 #include "ntt_mulkl.hpp"
+#include "ntt_pack.hpp"
 #include "ntt_round.hpp"
 #include "ntt_sample.hpp"
 #include "ntt_xof.hpp"
@@ -447,6 +448,48 @@ template <int PS> struct LRound {
     }
 };
 
+// poly_pack / poly_unpack (ntt_pack.hpp): poly_round's launch shape, a wave per
+// 1024 coefficients; the kernels are shared by the sets of equal n
+template <int PS> struct LPack {
+    static int run(uint32_t *bytes, uint32_t *w, uint32_t *mx, bool unpack, const PackRows &R, size_t npoly, hipStream_t s,
+                   const DevInfo &d)
+    {
+        constexpr int WPP = RoundGeom<PS>::WPP;
+        using G = PackGeom<WPP>;
+        const size_t nwaves = npoly * WPP;
+        const LaunchShape l = launch_shape(ceil_div(nwaves, G::WAVES), 1, d.cus, 8, ROUND_TILES_MAX);
+        const dim3 grid(l.grid), wg(G::WG);
+        if (!unpack) hipLaunchKernelGGL((k_poly_pack<WPP>), grid, wg, 0, s, bytes, (const uint32_t *)w, R, nwaves, l.chunk);
+        else if (mx) hipLaunchKernelGGL((k_poly_unpack<WPP, true>), grid, wg, 0, s, w, mx, (const uint32_t *)bytes, R, nwaves, l.chunk);
+        else hipLaunchKernelGGL((k_poly_unpack<WPP, false>), grid, wg, 0, s, w, mx, (const uint32_t *)bytes, R, nwaves, l.chunk);
+        return finish_launch();
+    }
+};
+
+// The checks of poly_pack / poly_unpack in the header's order, then the launch.
+// bytes: the packed rows; w: the coefficients; mx: poly_unpack's maxima or NULL.
+int pack_common(const void *bytes, const void *w, const void *mx, bool unpack, size_t stride, size_t batch, int k, int bits,
+                int sgn, int ps, void *stream)
+{
+    const ParamSet *p = param_set(ps);
+    if (!p || k < 1 || k > NTT_MUL_K_MAX || (sgn != 0 && sgn != 1)) return NTT_ERR_PARAM;
+    int qbits = 0;
+    while (p->q >> qbits) ++qbits;
+    if (bits < 8 || bits > qbits - sgn) return NTT_ERR_PARAM;
+    const size_t packed = (size_t)k * p->n * (size_t)bits / 8;
+    if ((stride & 15u) || stride < packed) return NTT_ERR_PARAM;
+    if (batch == 0) return NTT_OK;
+    if (!bytes || !w) return NTT_ERR_NULL;
+    if (((((uintptr_t)bytes) | ((uintptr_t)w)) & 15u) || (((uintptr_t)mx) & 3u)) return NTT_ERR_ALIGN;
+    if (batch > (size_t)0x7FFFFFFF / (size_t)k) return NTT_ERR_SIZE;
+    const size_t bbytes = (batch - 1) * stride + packed, wbytes = batch * k * p->n * 4, mbytes = batch * k * 4;
+    if (ranges_overlap(bytes, bbytes, w, wbytes)) return NTT_ERR_ALIAS;
+    if (mx && (ranges_overlap(mx, mbytes, bytes, bbytes) || ranges_overlap(mx, mbytes, w, wbytes))) return NTT_ERR_ALIAS;
+    const PackRows R = {stride, (uint32_t)k, (uint32_t)bits, sgn ? 1u << (bits - 1) : 0u, p->q,
+                        (uint32_t)(((uint64_t)1 << 32) / (uint32_t)bits) + 1u};
+    return launch<LPack>(ps, (uint32_t *)bytes, (uint32_t *)w, (uint32_t *)mx, unpack, R, batch * k, (hipStream_t)stream);
+}
+
 // largest hi of poly_round: it fits a signed byte iff this is <= 127
 uint32_t round_hmax(uint32_t q, int d) { return ((q - 1) / 2 + (1u << (d - 1)) - 1) >> d; }
 
@@ -746,6 +789,17 @@ int poly_sample_y(uint32_t *d_y, const uint8_t *d_seed, size_t seedlen, const ui
                            (const uint64_t *)d_seed, sw, d_nonce, nonce, (uint32_t)batch, p->n, p->q, (uint32_t)bits,
                            (uint32_t)NTT_SAMPLE_Y_REFILLS_MAX);
     return finish_launch();
+}
+
+int poly_pack(uint8_t *d_out, size_t stride, const uint32_t *d_w, size_t batch, int k, int bits, int sgn, int ps, void *stream)
+{
+    return pack_common(d_out, d_w, nullptr, false, stride, batch, k, bits, sgn, ps, stream);
+}
+
+int poly_unpack(uint32_t *d_w, uint32_t *d_max, const uint8_t *d_in, size_t stride, size_t batch, int k, int bits, int sgn,
+                int ps, void *stream)
+{
+    return pack_common(d_in, d_w, d_max, true, stride, batch, k, bits, sgn, ps, stream);
 }
 
 int poly_mul_nussbaumer(uint32_t *d_c, const uint32_t *d_a, const uint32_t *d_b, size_t batch, int ps, int ring,

@@ -95,6 +95,8 @@ def lib():
         L.ntt_xof.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_challenge.argtypes = [_vp, _vp, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_sample_y.argtypes = [_vp, _vp, _sz, _vp, ctypes.c_uint32, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
+        L.poly_pack.argtypes = [_vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
+        L.poly_unpack.argtypes = [_vp, _vp, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_mul_nussbaumer.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.ntt_fill_uniform.argtypes = [_vp, _sz, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, _vp]
         L.ntt_last_hip_error.restype = ctypes.c_int
@@ -676,6 +678,69 @@ def poly_sample_y(y, seed, param_set, bits: int, algo="shake256", nonce: int = 0
     _run("poly_sample_y", tensors, stream,
          lambda s: fn(y.data_ptr(), seed.data_ptr(), seedlen, pn, int(nonce), nb, int(bits), a, _ps(param_set), s))
     return y
+
+
+def _pack_operands(rows, w, param_set, bits, signed, maxima=None):
+    """The operands of poly_pack / poly_unpack, checked: batch, stride, k, sgn
+    and the tensors given, for _run.  rows is int8/uint8 [batch, stride], w
+    int32 [batch, k, n] or [batch, n], maxima None or int32 with batch*k
+    elements."""
+    torch = _torch()
+    info = param_info(param_set)
+    n, qbits = info["n"], info["q"].bit_length()
+    _batch(rows, 1, (torch.int8, torch.uint8), "int8/uint8")   # device, dtype, contiguity
+    if rows.dim() != 2:
+        raise ValueError(f"rows: shape {tuple(rows.shape)}, expected [batch, stride]")
+    nb, stride = rows.shape
+    _batch(w, n)
+    if w.dim() < 2 or w.shape[0] != nb:
+        raise ValueError(f"w: shape {tuple(w.shape)}, expected [{nb}, k, {n}] or [{nb}, {n}]")
+    k = w.numel() // (nb * n) if nb else 1
+    if w.numel() != nb * k * n or not 1 <= k <= MUL_K_MAX:
+        raise ValueError(f"w: numel {w.numel()} is not batch*k*n = {nb}*k*{n} with 1 <= k <= {MUL_K_MAX}")
+    sgn = 1 if signed else 0
+    if not 8 <= int(bits) <= qbits - sgn:
+        raise ValueError(f"bits = {bits}, expected 8 .. {qbits - sgn} ({'signed' if sgn else 'unsigned'})")
+    packed = k * n * int(bits) // 8
+    if stride % 16 or stride < packed:
+        raise ValueError(f"rows: stride {stride}, expected a multiple of 16 and >= k*n*bits/8 = {packed}")
+    tensors = (rows, w)
+    if maxima is not None:
+        if _batch(maxima, 1) != nb * k:
+            raise ValueError(f"maxima: numel {maxima.numel()} is not batch*k = {nb}*{k}")
+        tensors = (rows, w, maxima)
+    return nb, stride, k, sgn, tensors
+
+
+def poly_pack(out, w, param_set, bits: int, signed=True, stream=None):
+    """qTESLA's wire format: the coefficients w, int32 [batch, k, n] (or
+    [batch, n] for k = 1; entries < 2q), as fields of `bits` bits in the rows
+    out, int8/uint8 [batch, stride] with stride a multiple of 16 and
+    >= k*n*bits/8.  signed: the centred value's two's-complement low bits (a
+    signature's z: bits = 20 for p-I, 22 for p-III); unsigned: the canonical
+    value's low bits (a public key's t: bits = 29 / 30).  A value outside the
+    field's range is truncated.  Bytes of a row beyond k*n*bits/8 are not
+    written.  8 <= bits <= bit length of q, less one when signed.  Returns out."""
+    nb, stride, k, sgn, tensors = _pack_operands(out, w, param_set, bits, signed)
+    fn = lib().poly_pack
+    _run("poly_pack", tensors, stream,
+         lambda s: fn(out.data_ptr(), stride, w.data_ptr(), nb, k, int(bits), sgn, _ps(param_set), s))
+    return out
+
+
+def poly_unpack(w, inp, param_set, bits: int, signed=True, maxima=None, stream=None):
+    """poly_pack's inverse: the rows inp, int8/uint8 [batch, stride], to
+    canonical coefficients w, int32 [batch, k, n] (or [batch, n]).  maxima,
+    None or int32 with batch*k elements, receives per polynomial max |s| of
+    the sign-extended fields (signed) or the largest raw field (unsigned: a
+    maximum >= q is a malformed key).  Bytes of a row beyond k*n*bits/8 are not
+    read.  Returns (w, maxima)."""
+    nb, stride, k, sgn, tensors = _pack_operands(inp, w, param_set, bits, signed, maxima)
+    fn = lib().poly_unpack
+    pm = None if maxima is None else maxima.data_ptr()
+    _run("poly_unpack", tensors, stream,
+         lambda s: fn(w.data_ptr(), pm, inp.data_ptr(), stride, nb, k, int(bits), sgn, _ps(param_set), s))
+    return w, maxima
 
 
 def poly_mul_nussbaumer(c, a, b, param_set, ring="q", stream=None):
