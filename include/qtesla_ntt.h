@@ -349,6 +349,61 @@ int poly_sample_y(uint32_t *d_y, const uint8_t *d_seed, size_t seedlen,
                   const uint32_t *d_nonce, uint32_t nonce, size_t batch,
                   int bits, int algo, int param_set, void *stream);
 
+/* qTESLA's GenA: seed_a to the k public polynomials a_1 .. a_k, so that a
+ * verifier that holds only public-key bytes, and a key-generation batch, make
+ * their rows on the device.  qTESLA samples a directly in the NTT domain: the
+ * output is exactly the d_ahat that poly_mul_ntt_k / _kl / _kl_round take.
+ *   d_seed [batch][seedlen] bytes
+ *   d_a    polynomial i of key b starts at word (b * k + i) * pstride; its n
+ *          words are each written exactly once, by plain vector stores; the
+ *          pstride - n words after it are never written.  pstride = n is the
+ *          dense [batch][k][n] of poly_mul_ntt_k; pstride = 2 n writes slot 0
+ *          of poly_mul_ntt_kl's [k][2][n] rows in place, beside q - t-hat.
+ * Each seed on its own.  q and n are param_set's, qbits is the bit length of
+ * q, nbytes = (qbits + 7) / 8, mask = 2^qbits - 1, and cshake128_simple is
+ * ntt_xof's, with rate 168 (poly_uniform of qTESLA round 2, restated from
+ * memory; this statement, not the upstream file, is what the tests bind):
+ *   buf = cshake128_simple(seed, outlen = 168 * nblocks, cstm = 0);  nb = nblocks;  pos = 0;  dmsp = 1;  i = 0
+ *   while i < k * n:
+ *       if pos > 168 * nb - 4 * nbytes:
+ *           nb = 1;  buf = cshake128_simple(seed, outlen = 168, cstm = dmsp);  dmsp += 1;  pos = 0
+ *       four times:  v = le32(buf + pos) & mask;  pos += nbytes
+ *                    if v < q and i < k * n:  a[i / n][i % n] = v;  i += 1
+ * Flat draw stream: a call of nb blocks gives 4 * floor(168 * nb / (4 * nbytes))
+ * draws; for nbytes = 4 a refill block is 40 draws with words 40 and 41 unused,
+ * and an odd nblocks also leaves its last two words unused.
+ * The values are the plain v, canonical in [0, q), in natural order.  Upstream
+ * multiplies each by a Montgomery constant of its own NTT, which is
+ * representation and not scheme.
+ * nblocks is the caller's (the library keeps no scheme constants; qTESLA's
+ * PARAM_GEN_A is 108 for p-I and 180 for p-III), 1 <= nblocks <=
+ * NTT_GEN_A_BLOCKS_MAX.
+ * Refills are bounded: refills_max(k, n) = min(65535, 4 * ceil(k n / 40)) (no
+ * unbounded loop on the device, and cstm never leaves 16 bits).  q >=
+ * 2^(qbits-1), so a draw is accepted with probability >= 1/2 and the bound
+ * allows at least twice the draws the worst prime needs on average: hash
+ * outputs cannot reach it.  Were it reached, the coefficients not yet drawn
+ * get 0.
+ * Parameter sets: those with nbytes = 4 (p-I, p-III, p-III-4096, p-III-8192),
+ * where every draw is one whole 32-bit word of the squeezed state.  `ref` has
+ * a 24-bit prime, would need three-byte draws and is not a qTESLA set:
+ * NTT_ERR_PARAM.
+ * Checks, in this order (the first defect decides):
+ *   NTT_ERR_PARAM  unknown param_set, or ref; k outside 1 .. NTT_MUL_K_MAX;
+ *                  nblocks outside 1 .. 256; seedlen not a multiple of 8 or
+ *                  outside 8 .. 160 (one absorb block; qTESLA: 32);
+ *                  pstride < n or not a multiple of 4
+ *   batch == 0     NTT_OK, nothing else is looked at
+ *   NTT_ERR_NULL   d_a, d_seed
+ *   NTT_ERR_ALIGN  d_a 16-byte, d_seed 8-byte
+ *   NTT_ERR_SIZE   batch > 2^31 - 1
+ *   NTT_ERR_ALIAS  d_a's extent, ((batch k - 1) pstride + n) words, overlaps
+ *                  the seeds
+ * One seed per lane, as ntt_xof: the throughput comes from the batch. */
+#define NTT_GEN_A_BLOCKS_MAX 256
+int poly_gen_a(uint32_t *d_a, size_t pstride, const uint8_t *d_seed, size_t seedlen,
+               size_t batch, int k, int nblocks, int param_set, void *stream);
+
 /* qTESLA's wire formats: coefficients to bit-packed rows and back -- a
  * signature's z as n fields of B_BITS + 1 bits (p-I: 20, p-III: 22), a public
  * key's t as k n fields of ceil(log2 q) bits (29 / 30) -- so that signature

@@ -23,6 +23,7 @@
 #include "ntt_mulkl.hpp"
 #include "ntt_pack.hpp"
 #include "ntt_round.hpp"
+#include "ntt_gen_a.hpp"
 #include "ntt_sample.hpp"
 #include "ntt_xof.hpp"
 #include "ntt_internal.h"
@@ -788,6 +789,33 @@ int poly_sample_y(uint32_t *d_y, const uint8_t *d_seed, size_t seedlen, const ui
         hipLaunchKernelGGL(k_sample_y<XOF_RATE256>, grid, wg, 0, (hipStream_t)stream, d_y,
                            (const uint64_t *)d_seed, sw, d_nonce, nonce, (uint32_t)batch, p->n, p->q, (uint32_t)bits,
                            (uint32_t)NTT_SAMPLE_Y_REFILLS_MAX);
+    return finish_launch();
+}
+
+int poly_gen_a(uint32_t *d_a, size_t pstride, const uint8_t *d_seed, size_t seedlen, size_t batch, int k, int nblocks, int ps,
+               void *stream)
+{
+    const ParamSet *p = param_set(ps);
+    if (!p) return NTT_ERR_PARAM;
+    uint32_t qbits = 0;
+    while (qbits < 32 && (p->q >> qbits)) ++qbits;
+    if (qbits <= 24) return NTT_ERR_PARAM;   // four-byte draws only: `ref` would need three
+    if (k < 1 || k > NTT_MUL_K_MAX || nblocks < 1 || nblocks > NTT_GEN_A_BLOCKS_MAX) return NTT_ERR_PARAM;
+    if ((seedlen & 7u) || seedlen < 8 || seedlen > 160) return NTT_ERR_PARAM;   // one absorb block
+    if (pstride < p->n || (pstride & 3u)) return NTT_ERR_PARAM;
+    if (batch == 0) return NTT_OK;
+    if (!d_a || !d_seed) return NTT_ERR_NULL;
+    if ((((uintptr_t)d_a) & 15u) || (((uintptr_t)d_seed) & 7u)) return NTT_ERR_ALIGN;
+    if (batch > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
+    const size_t abytes = ((batch * (size_t)k - 1) * pstride + p->n) * 4;
+    if (ranges_overlap(d_a, abytes, d_seed, batch * seedlen)) return NTT_ERR_ALIAS;
+    int rc;
+    DevInfo *d = nullptr;
+    if ((rc = device_ready(&d)) != NTT_OK) return rc;
+    const size_t kn = (size_t)k * p->n, refills = 4 * ceil_div(kn, (size_t)40);
+    hipLaunchKernelGGL(k_gen_a, dim3((uint32_t)ceil_div(batch, (size_t)GEN_A_WG)), dim3(GEN_A_WG), 0, (hipStream_t)stream, d_a,
+                       pstride, (const uint64_t *)d_seed, (uint32_t)(seedlen / 8), (uint32_t)batch, (uint32_t)k, p->logn, p->q,
+                       (uint32_t)((1ull << qbits) - 1), (uint32_t)nblocks, (uint32_t)(refills < 65535 ? refills : 65535));
     return finish_launch();
 }
 

@@ -95,6 +95,7 @@ def lib():
         L.ntt_xof.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_challenge.argtypes = [_vp, _vp, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_sample_y.argtypes = [_vp, _vp, _sz, _vp, ctypes.c_uint32, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
+        L.poly_gen_a.argtypes = [_vp, _sz, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_pack.argtypes = [_vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_unpack.argtypes = [_vp, _vp, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_mul_nussbaumer.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
@@ -576,6 +577,7 @@ XOF_ALGOS = {"shake128": 0, "shake256": 1}   # NTT_XOF_SHAKE128, NTT_XOF_SHAKE25
 XOF_OUT_MAX = 512          # NTT_XOF_OUT_MAX
 CHALLENGE_H_MAX = 128      # NTT_CHALLENGE_H_MAX
 SAMPLE_Y_REFILLS_MAX = 255   # NTT_SAMPLE_Y_REFILLS_MAX
+GEN_A_BLOCKS_MAX = 256       # NTT_GEN_A_BLOCKS_MAX
 
 
 def _byte_rows(name: str, t, batch: int) -> int:
@@ -678,6 +680,40 @@ def poly_sample_y(y, seed, param_set, bits: int, algo="shake256", nonce: int = 0
     _run("poly_sample_y", tensors, stream,
          lambda s: fn(y.data_ptr(), seed.data_ptr(), seedlen, pn, int(nonce), nb, int(bits), a, _ps(param_set), s))
     return y
+
+
+def poly_gen_a(a, seed, param_set, nblocks: int, k: int, pstride=None, stream=None):
+    """qTESLA's GenA: seed [batch, seedlen] int8/uint8 (seedlen a multiple of 8
+    within 8 .. 160; qTESLA: seed_a's 32 bytes) to the k public polynomials of
+    each key, canonical in [0, q) and already in the NTT domain: what
+    poly_mul_ntt_k / _kl / _kl_round take as ahat.  a is an int32 contiguous
+    device tensor of batch*k*pstride elements; polynomial i of key b starts at
+    element (b*k + i)*pstride and the pstride - n elements after it are not
+    written.  pstride defaults to n (dense [batch, k, n]); pstride = 2n fills
+    slot 0 of [k, 2, n] verification rows in place.  nblocks is qTESLA's
+    PARAM_GEN_A (108 for p-I, 180 for p-III), 1 .. 256.  Every parameter set
+    but "ref".  Returns a."""
+    n = _n(param_set)
+    _batch(a, 1)   # device, dtype, contiguity
+    if not 1 <= int(k) <= MUL_K_MAX:
+        raise ValueError(f"k = {k}, expected 1 .. {MUL_K_MAX}")
+    if not 1 <= int(nblocks) <= GEN_A_BLOCKS_MAX:
+        raise ValueError(f"nblocks = {nblocks}, expected 1 .. {GEN_A_BLOCKS_MAX}")
+    pstride = n if pstride is None else int(pstride)
+    if pstride < n or pstride % 4:
+        raise ValueError(f"pstride = {pstride}, expected a multiple of 4 and >= n = {n}")
+    if seed.dim() != 2:
+        raise ValueError(f"seed: shape {tuple(seed.shape)}, expected [batch, 8 .. 160]")
+    nb = seed.shape[0]
+    seedlen = _byte_rows("seed", seed, nb)
+    if not 8 <= seedlen <= 160:
+        raise ValueError(f"seed: shape {tuple(seed.shape)}, expected [{nb}, 8 .. 160]")
+    if a.numel() != nb * int(k) * pstride:
+        raise ValueError(f"a: numel {a.numel()} is not batch*k*pstride = {nb}*{k}*{pstride}")
+    fn = lib().poly_gen_a
+    _run("poly_gen_a", (a, seed), stream,
+         lambda s: fn(a.data_ptr(), pstride, seed.data_ptr(), seedlen, nb, int(k), int(nblocks), _ps(param_set), s))
+    return a
 
 
 def _pack_operands(rows, w, param_set, bits, signed, maxima=None):
