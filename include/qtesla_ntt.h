@@ -242,6 +242,40 @@ int poly_mul_ntt_kl_round(uint8_t *d_hi, uint32_t *d_norms, const uint32_t *cons
                           const uint32_t *d_ahat, const uint32_t *d_add, size_t batch,
                           int k, int l, int d, int param_set, void *stream);
 
+/* poly_mul_ntt_kl and poly_mul_ntt_kl_round over many keys, one launch: every
+ * message of the batch names the key whose rows it is multiplied by -- a
+ * verifier's batch of signatures made under different public keys, or (l = 1,
+ * d_key NULL) a key-generation batch's t_b = a_b * s_b + e_b with one a per key.
+ *   d_ahat  [nkeys][k][l][n]  key j's block is exactly the [k][l][n] the unkeyed
+ *           entry point takes, entries < 2q; there is no stride between keys.
+ *           l = 2: poly_gen_a(batch = nkeys, pstride = 2n) fills slot 0 of all
+ *           keys in one call; l = 1: poly_gen_a's dense output is d_ahat as it lies
+ *   d_key   NULL, or [batch] uint32: message b uses key
+ *               min(d_key ? d_key[b] : b, nkeys - 1)
+ *           The minimum is the definition, not an error path: the device cannot
+ *           return an error, and no index makes the kernel read outside d_ahat.
+ *           An index >= nkeys is the caller's bug, and its result is the last
+ *           key's.  With d_key NULL and nkeys >= batch, message b is under key b.
+ * Everything else -- d_y, d_add, d_out / d_hi / d_norms, k, l, d, the n = 1024 /
+ * 2048 restriction, NULL outputs and the byte-range rule of d -- is as in the
+ * unkeyed entry point of the same name; with every index equal to j the result
+ * is bit-identical to that call on key j's block.  Both l run the same kernel,
+ * in the launch shape of ntt_mul_kl_shape(param_set, 2, ...).
+ * The checks follow the unkeyed entry point's order, with
+ *   NTT_ERR_PARAM  also for nkeys == 0 (an empty batch is NTT_OK after that)
+ *   NTT_ERR_ALIGN  d_key not 4-byte aligned (NULL is accepted)
+ *   NTT_ERR_SIZE   also for nkeys > NTT_MUL_KEYS_MAX = 2^31 - 1
+ *   NTT_ERR_ALIAS  an output overlaps d_key's batch words or any of d_ahat's
+ *                  nkeys*k*l*n words; d_key may overlap the other inputs. */
+#define NTT_MUL_KEYS_MAX 2147483647
+int poly_mul_ntt_kl_keyed(uint32_t *d_out, const uint32_t *const *d_y, const uint32_t *d_ahat,
+                          const uint32_t *d_key, size_t nkeys, const uint32_t *d_add,
+                          size_t batch, int k, int l, int param_set, void *stream);
+int poly_mul_ntt_kl_round_keyed(uint8_t *d_hi, uint32_t *d_norms, const uint32_t *const *d_y,
+                                const uint32_t *d_ahat, const uint32_t *d_key, size_t nkeys,
+                                const uint32_t *d_add, size_t batch, int k, int l, int d,
+                                int param_set, void *stream);
+
 /* SHAKE128 / SHAKE256 / qTESLA's cshake*_simple over a batch, one launch --
  * qTESLA's H and G on the device, so that the hi bytes poly_mul_ntt_kl_round
  * writes never leave it:

@@ -168,10 +168,14 @@ int check_abc(int ps, const uint32_t *a, const uint32_t *b, const uint32_t *c, s
 
 // The inputs (y_0 .. y_{l-1}, ahat, add) of poly_mul_ntt_k / _kl / _kl_round:
 // l batches of polynomials, the k x l shared rows and the optional addend.
+// The keyed entry points add key (NULL or [batch] indices) and nkeys, the
+// number of [k][l][n] blocks in ahat (1 in the unkeyed ones).
 struct RowOps {
     const uint32_t *const *y;
     int l;
     const uint32_t *ahat, *add;
+    const uint32_t *key = nullptr;
+    size_t nkeys = 1;
     bool null() const
     {
         if (!y || !ahat) return true;
@@ -181,33 +185,37 @@ struct RowOps {
     }
     uintptr_t bits() const   // every address ORed, for the alignment test; after null()
     {
-        uintptr_t b = ((uintptr_t)ahat) | ((uintptr_t)add);
+        uintptr_t b = ((uintptr_t)ahat) | ((uintptr_t)add) | ((uintptr_t)key);
         for (int j = 0; j < l; j++) b |= (uintptr_t)y[j];
         return b;
     }
-    // [x, x + bytes) against every y_j and ahat (the addend has its own rule per entry point)
+    bool too_large(size_t batch) const { return batch > (size_t)0x7FFFFFFF || nkeys > (size_t)NTT_MUL_KEYS_MAX; }
+    // [x, x + bytes) against every y_j, all of ahat and the batch's key indices
+    // (the addend has its own rule per entry point)
     bool overlap(const void *x, size_t bytes, size_t batch, int k, size_t row) const
     {
         for (int j = 0; j < l; j++)
             if (ranges_overlap(x, bytes, y[j], batch * row)) return true;
-        return ranges_overlap(x, bytes, ahat, (size_t)k * l * row);
+        if (key && ranges_overlap(x, bytes, key, batch * 4)) return true;
+        return ranges_overlap(x, bytes, ahat, nkeys * k * l * row);
     }
 };
-// their parameter set (n = 1024 / 2048, the sets qTESLA defines), k and l; NULL: NTT_ERR_PARAM
-const ParamSet *row_param_set(int ps, int k, int l)
+// their parameter set (n = 1024 / 2048, the sets qTESLA defines), k, l and the
+// number of keys; NULL: NTT_ERR_PARAM
+const ParamSet *row_param_set(int ps, int k, int l, size_t nkeys = 1)
 {
     const ParamSet *p = param_set(ps);
-    return p && p->n <= 2048 && k >= 1 && k <= NTT_MUL_K_MAX && l >= 1 && l <= NTT_MUL_L_MAX ? p : nullptr;
+    return p && p->n <= 2048 && k >= 1 && k <= NTT_MUL_K_MAX && l >= 1 && l <= NTT_MUL_L_MAX && nkeys >= 1 ? p : nullptr;
 }
-// poly_mul_ntt_k / _kl: PARAM, empty batch (NTT_OK, as check_abc), NULL, ALIGN, SIZE, ALIAS
+// poly_mul_ntt_k / _kl / _kl_keyed: PARAM, empty batch (NTT_OK, as check_abc), NULL, ALIGN, SIZE, ALIAS
 int check_mul_kl(const uint32_t *out, const RowOps &o, size_t batch, int k, int ps)
 {
-    const ParamSet *p = row_param_set(ps, k, o.l);
+    const ParamSet *p = row_param_set(ps, k, o.l, o.nkeys);
     if (!p) return NTT_ERR_PARAM;
     if (batch == 0) return NTT_OK;
     if (!out || o.null()) return NTT_ERR_NULL;
     if ((((uintptr_t)out) | o.bits()) & 3u) return NTT_ERR_ALIGN;
-    if (batch > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
+    if (o.too_large(batch)) return NTT_ERR_SIZE;
     const size_t row = (size_t)p->n * 4, obytes = batch * k * row;
     if (o.overlap(out, obytes, batch, k, row)) return NTT_ERR_ALIAS;
     if (o.add && partial_overlap(o.add, out, obytes)) return NTT_ERR_ALIAS;
@@ -427,6 +435,34 @@ template <int PS> struct LMulKLRound {
     }
 };
 
+// poly_mul_ntt_kl_keyed (ro NULL) and poly_mul_ntt_kl_round_keyed (out NULL):
+// the keyed kernels of ntt_mulkl.hpp, in LMulKLRound's launch shape -- the
+// split threshold is poly_mul_ntt_kl's at l = 2, not swept again -- for both l
+template <int PS> struct LMulKLKeyed {
+    template <int L>
+    static void launch(const MulKLIn<L> &in, const uint32_t *ahat, const KeySel &ks, const uint32_t *add, uint32_t *out,
+                       const RoundOut *ro, size_t batch, int k, hipStream_t s, const RowShape &r)
+    {
+        with_flag(add != nullptr, [&](auto ad) {
+            constexpr bool ADD = decltype(ad)::value;
+            if (ro)
+                hipLaunchKernelGGL((k_poly_mul_kl_round_keyed<PS, L, ADD>), r.grid, dim3(MULKL_WG), 0, s, in, ahat, ks, add, *ro,
+                                   (uint32_t)batch, (uint32_t)k, r.ppw);
+            else
+                hipLaunchKernelGGL((k_poly_mul_kl_keyed<PS, L, ADD>), r.grid, dim3(MULKL_WG), 0, s, in, ahat, ks, add, out,
+                                   (uint32_t)batch, (uint32_t)k, r.ppw);
+        });
+    }
+    static int run(const RowOps &o, uint32_t *out, const RoundOut *ro, size_t batch, int k, hipStream_t s, const DevInfo &d)
+    {
+        const RowShape r = row_shape<PS>(batch, k, MULKL_WAVES, MULKL_PPW_MAX, mulkl_split_max(PS), d);
+        const KeySel ks = {o.key, (uint32_t)(o.nkeys - 1)};
+        if (o.l == 1) launch<1>(MulKLIn<1>{{o.y[0]}}, o.ahat, ks, o.add, out, ro, batch, k, s, r);
+        else launch<2>(MulKLIn<2>{{o.y[0], o.y[1]}}, o.ahat, ks, o.add, out, ro, batch, k, s, r);
+        return finish_launch();
+    }
+};
+
 // poly_round (ntt_round.hpp): a workgroup per tile of RoundGeom's WAVES
 // kilo-coefficients, up to ROUND_TILES_MAX consecutive tiles each once there
 // are 8 workgroups per CU
@@ -520,6 +556,37 @@ int mul_common(uint32_t *d_c, const uint32_t *d_a, const uint32_t *d_b, size_t b
     int rc = check_abc(ps, d_a, d_b, d_c, batch);
     if (rc != NTT_OK || batch == 0) return rc;
     return launch<LMul>(ps, d_a, d_b, d_c, batch, (hipStream_t)stream, bhat);
+}
+
+// poly_mul_ntt_kl_round and its keyed form: the checks, then the launch
+int mul_kl_round_common(uint8_t *d_hi, uint32_t *d_norms, const RowOps &in, bool keyed, size_t batch, int k, int d,
+                        int ps, void *stream)
+{
+    // poly_round's order, not poly_mul_ntt_kl's: the inputs' alignment after the outputs' checks
+    const ParamSet *p = row_param_set(ps, k, in.l, in.nkeys);
+    if (!p || d < 1 || d > 30) return NTT_ERR_PARAM;
+    if (batch == 0) return NTT_OK;
+    if (in.null()) return NTT_ERR_NULL;
+    if (in.too_large(batch)) return NTT_ERR_SIZE;
+    const size_t row = (size_t)p->n * 4, hbytes = batch * k * p->n, nbytes = batch * k * 8;
+    int rc;
+    if ((rc = check_round_out(p, d_hi, d_norms, d, hbytes, nbytes)) != NTT_OK) return rc;
+    if (in.bits() & 3u) return NTT_ERR_ALIGN;
+    // neither output overlaps any input (the addend included: nothing is accumulated in place)
+    const void *outs[2] = {d_hi, d_norms};
+    const size_t obytes[2] = {hbytes, nbytes};
+    for (int o = 0; o < 2; o++) {
+        if (!outs[o]) continue;
+        if (in.overlap(outs[o], obytes[o], batch, k, row)) return NTT_ERR_ALIAS;
+        if (in.add && ranges_overlap(outs[o], obytes[o], in.add, batch * k * row)) return NTT_ERR_ALIAS;
+    }
+    const RoundOut ro = {d_hi, (uint2 *)d_norms, (uint32_t)d};
+    if (keyed) {
+        uint32_t *const no_out = nullptr;
+        const RoundOut *const pro = &ro;
+        return launch<LMulKLKeyed, LARGE_PS0>(ps, in, no_out, pro, batch, k, (hipStream_t)stream);
+    }
+    return launch<LMulKLRound, LARGE_PS0>(ps, in.y, in.l, in.ahat, in.add, ro, batch, k, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -684,27 +751,24 @@ int poly_round(uint8_t *d_hi, uint32_t *d_norms, const uint32_t *d_w, size_t bat
 int poly_mul_ntt_kl_round(uint8_t *d_hi, uint32_t *d_norms, const uint32_t *const *d_y, const uint32_t *d_ahat,
                           const uint32_t *d_add, size_t batch, int k, int l, int d, int ps, void *stream)
 {
-    // poly_round's order, not poly_mul_ntt_kl's: the inputs' alignment after the outputs' checks
-    const ParamSet *p = row_param_set(ps, k, l);
-    if (!p || d < 1 || d > 30) return NTT_ERR_PARAM;
-    if (batch == 0) return NTT_OK;
-    const RowOps in = {d_y, l, d_ahat, d_add};
-    if (in.null()) return NTT_ERR_NULL;
-    if (batch > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
-    const size_t row = (size_t)p->n * 4, hbytes = batch * k * p->n, nbytes = batch * k * 8;
-    int rc;
-    if ((rc = check_round_out(p, d_hi, d_norms, d, hbytes, nbytes)) != NTT_OK) return rc;
-    if (in.bits() & 3u) return NTT_ERR_ALIGN;
-    // neither output overlaps any input (the addend included: nothing is accumulated in place)
-    const void *outs[2] = {d_hi, d_norms};
-    const size_t obytes[2] = {hbytes, nbytes};
-    for (int o = 0; o < 2; o++) {
-        if (!outs[o]) continue;
-        if (in.overlap(outs[o], obytes[o], batch, k, row)) return NTT_ERR_ALIAS;
-        if (d_add && ranges_overlap(outs[o], obytes[o], d_add, batch * k * row)) return NTT_ERR_ALIAS;
-    }
-    const RoundOut ro = {d_hi, (uint2 *)d_norms, (uint32_t)d};
-    return launch<LMulKLRound, LARGE_PS0>(ps, d_y, l, d_ahat, d_add, ro, batch, k, (hipStream_t)stream);
+    return mul_kl_round_common(d_hi, d_norms, RowOps{d_y, l, d_ahat, d_add}, false, batch, k, d, ps, stream);
+}
+
+int poly_mul_ntt_kl_keyed(uint32_t *d_out, const uint32_t *const *d_y, const uint32_t *d_ahat, const uint32_t *d_key,
+                          size_t nkeys, const uint32_t *d_add, size_t batch, int k, int l, int ps, void *stream)
+{
+    const RowOps in = {d_y, l, d_ahat, d_add, d_key, nkeys};
+    int rc = check_mul_kl(d_out, in, batch, k, ps);
+    if (rc != NTT_OK || batch == 0) return rc;
+    const RoundOut *const no_ro = nullptr;
+    return launch<LMulKLKeyed, LARGE_PS0>(ps, in, d_out, no_ro, batch, k, (hipStream_t)stream);
+}
+
+int poly_mul_ntt_kl_round_keyed(uint8_t *d_hi, uint32_t *d_norms, const uint32_t *const *d_y, const uint32_t *d_ahat,
+                                const uint32_t *d_key, size_t nkeys, const uint32_t *d_add, size_t batch, int k, int l,
+                                int d, int ps, void *stream)
+{
+    return mul_kl_round_common(d_hi, d_norms, RowOps{d_y, l, d_ahat, d_add, d_key, nkeys}, true, batch, k, d, ps, stream);
 }
 
 int ntt_xof(uint8_t *d_out, size_t outlen, const uint8_t *d_in0, size_t len0, const uint8_t *d_in1, size_t len1,

@@ -31,6 +31,10 @@
 // k_poly_mul_kl_round is the same kernel with poly_round (ntt_round.hpp) as
 // its store epilogue: both are ntt_mulkl_body.hpp, which says how.
 //
+// k_poly_mul_kl_keyed / k_poly_mul_kl_round_keyed are the same two kernels with
+// one block of rows per key, ahat [nkeys][k][l][n], and an index per message
+// (KeySel): the row base moves by key * (k l n) words and nothing else changes.
+//
 // Also here: k_poly_scatter, sparse (position, value) lists -> dense
 // polynomials (qTESLA's challenge c).
 #pragma once
@@ -92,6 +96,14 @@ struct RoundOut {
     uint32_t d;
 };
 
+// The keyed kernels' key of each message: message b takes the rows of key
+// min(key ? key[b] : b, last), last = nkeys - 1.  The clamp is the definition
+// (qtesla_ntt.h): whatever the index, the rows read lie inside ahat.
+struct KeySel {
+    const uint32_t *key;   // [npoly], or NULL
+    uint32_t last;
+};
+
 template <int PS, int L, bool ADD>
 __global__ __launch_bounds__(MULKL_WG, MULKL_WAVES_PER_SIMD) void k_poly_mul_kl(const MulKLIn<L> in,
                                                                                 const uint32_t *__restrict__ ahat,
@@ -99,7 +111,9 @@ __global__ __launch_bounds__(MULKL_WG, MULKL_WAVES_PER_SIMD) void k_poly_mul_kl(
                                                                                 uint32_t npoly, uint32_t k, uint32_t ppw)
 {
     constexpr bool RND = false;
+    constexpr bool KEYED = false;
     const RoundOut ro = {};
+    const KeySel ks = {};
 #include "ntt_mulkl_body.hpp"
 }
 
@@ -114,6 +128,36 @@ __global__ __launch_bounds__(MULKL_WG, MULKL_WAVES_PER_SIMD) void k_poly_mul_kl_
                                                                                       uint32_t ppw)
 {
     constexpr bool RND = true;
+    constexpr bool KEYED = false;
+    uint32_t *const out = nullptr;
+    const KeySel ks = {};
+#include "ntt_mulkl_body.hpp"
+}
+
+// poly_mul_ntt_kl_keyed / _kl_round_keyed: the two kernels above with ahat
+// [nkeys][k][L][n] and the key of each message (ks), at the same launch bounds
+// and launch shape.  L = 1 with ks.key NULL is a key-generation batch's
+// t_b = a_b s_b + e_b.
+template <int PS, int L, bool ADD>
+__global__ __launch_bounds__(MULKL_WG, MULKL_WAVES_PER_SIMD) void k_poly_mul_kl_keyed(const MulKLIn<L> in,
+                                                                                      const uint32_t *__restrict__ ahat,
+                                                                                      const KeySel ks, const uint32_t *add,
+                                                                                      uint32_t *out, uint32_t npoly, uint32_t k,
+                                                                                      uint32_t ppw)
+{
+    constexpr bool RND = false;
+    constexpr bool KEYED = true;
+    const RoundOut ro = {};
+#include "ntt_mulkl_body.hpp"
+}
+
+template <int PS, int L, bool ADD>
+__global__ __launch_bounds__(MULKL_WG, MULKL_WAVES_PER_SIMD) void k_poly_mul_kl_round_keyed(
+    const MulKLIn<L> in, const uint32_t *__restrict__ ahat, const KeySel ks, const uint32_t *add, const RoundOut ro,
+    uint32_t npoly, uint32_t k, uint32_t ppw)
+{
+    constexpr bool RND = true;
+    constexpr bool KEYED = true;
     uint32_t *const out = nullptr;
 #include "ntt_mulkl_body.hpp"
 }

@@ -1,6 +1,6 @@
-// ntt_mulkl_body.hpp -- the body of k_poly_mul_kl and k_poly_mul_kl_round
-// (ntt_mulkl.hpp), included into both function definitions; not a header of
-// its own.  It is text and not a function template because the code generated
+// ntt_mulkl_body.hpp -- the body of k_poly_mul_kl, k_poly_mul_kl_round and
+// their keyed forms (ntt_mulkl.hpp), included into the four function
+// definitions; not a header of its own.  It is text and not a function template because the code generated
 // for k_poly_mul_kl depends on the names of the symbols inside it (the LDS
 // array, the closure that inv_last_stage is instantiated with): moved into a
 // shared device function, or with a fourth template parameter on the kernel,
@@ -10,7 +10,16 @@
 //
 // Expects in scope: PS, L, ADD (template parameters); in, ahat, add, npoly, k,
 // ppw (kernel parameters); constexpr bool RND; uint32_t *out (RND off) and
-// const RoundOut ro (RND on), the other one a dummy.
+// const RoundOut ro (RND on), the other one a dummy; constexpr bool KEYED and
+// const KeySel ks (a dummy with KEYED off).
+//
+// KEYED: ahat is [nkeys][k][L][n] and the rows of a message are its key's, the
+// index read once per work unit.  n = 2048: a wave is one message, the index is
+// wave-uniform and stays in scalar registers.  n = 1024: the two half-waves are
+// two messages and each lane takes its own polynomial's index; the invalid half
+// of an odd batch's last unit takes the first polynomial's (Lane::load_poly), so
+// no word of ks.key at or past npoly is read.  Either way the index is clamped
+// to ks.last: no value of it takes a row load outside ahat.
 //
 // RND off: the row's canonical values are stored to `out`.  RND on: they are
 // rounded where they are computed (round_coeff, ntt_round.hpp) and never reach
@@ -36,6 +45,11 @@
     const uint32_t nunits = (npoly + LT::UPW - 1) / LT::UPW;
     const uint32_t kn = k * P::N;   // words between two polynomials of out / add (<= 2^14)
     uint32_t u = blockIdx.x * (MULKL_WAVES * ppw) + wave_id();
+    // KEYED, n = 1024: the index is per lane, so ks is kept in vector registers
+    // for the whole walk -- three scalar registers more across the unit loop
+    // spill one (ADD, RND off), and there are vector registers to spare
+    [[maybe_unused]] KeySel kv = ks;
+    if constexpr (KEYED && !LT::BIG) asm volatile("" : "+v"(kv.key), "+v"(kv.last));
 #pragma unroll 1
     for (uint32_t it = 0; it < ppw; ++it, u += MULKL_WAVES) {   // dispatch-ordered chunk (see chunk_loop)
         if (u >= nunits) break;
@@ -56,9 +70,17 @@
         const size_t ubase = (size_t)u * LT::UPW * kn;
         const uint32_t ooff = LT::BIG ? Ln.brl : Ln.h * kn + Ln.brl;
         const uint32_t aoff = valid ? ooff : Ln.brl;
+        size_t koff = 0;   // KEYED: words from ahat to the key's [k][L][n] block
+        if constexpr (KEYED) {
+            const uint32_t b = Ln.load_poly(u, npoly);   // < npoly
+            uint32_t key = kv.key != nullptr ? kv.key[b] : b;
+            if constexpr (LT::BIG) key = __builtin_amdgcn_readfirstlane(key);
+            koff = (size_t)min(key, kv.last) * ((size_t)kn * L);
+        }
 #pragma unroll 1
         for (uint32_t i = blockIdx.y; i < k; i += gridDim.y) {
             const uint32_t *pa = ahat + (size_t)i * (L * P::N) + Ln.brl;   // row i: a_i0-hat .. a_i(L-1)-hat, n words each
+            if constexpr (KEYED) pa += koff;
             uint32_t r[32];
 #pragma unroll
             for (int j = 0; j < 32; ++j) {

@@ -92,6 +92,10 @@ def lib():
         L.poly_round.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_mul_ntt_kl_round.argtypes = [_vp, _vp, ctypes.POINTER(_vp), _vp, _vp, _sz, ctypes.c_int, ctypes.c_int,
                                             ctypes.c_int, ctypes.c_int, _vp]
+        L.poly_mul_ntt_kl_keyed.argtypes = [_vp, ctypes.POINTER(_vp), _vp, _vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, _vp]
+        L.poly_mul_ntt_kl_round_keyed.argtypes = [_vp, _vp, ctypes.POINTER(_vp), _vp, _vp, _sz, _vp, _sz, ctypes.c_int,
+                                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
         L.ntt_xof.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_challenge.argtypes = [_vp, _vp, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_sample_y.argtypes = [_vp, _vp, _sz, _vp, ctypes.c_uint32, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
@@ -570,6 +574,69 @@ def poly_mul_ntt_kl_round(ys, ahat, param_set, d: int, hi=None, norms=None, add=
     pn = None if norms is None else norms.data_ptr()
     _run("poly_mul_ntt_kl_round", (*ins, *outs), stream,
          lambda s: fn(ph, pn, py, ahat.data_ptr(), pa, nb, k, l, int(d), _ps(param_set), s))
+    return hi, norms
+
+
+MUL_KEYS_MAX = 2**31 - 1   # NTT_MUL_KEYS_MAX
+
+
+def _keyed_operands(n: int, ys, ahat, keys, add, out=None):
+    """The operands of the keyed products, checked: _rows_operands on key 0's
+    block, then ahat's (nkeys, k, l, n) shape and keys, None or int32 [batch] on
+    the same device.  Returns _rows_operands' tuple with keys' pointer or None
+    and nkeys appended, keys among the tensors."""
+    torch = _torch()
+    ys = tuple(ys)
+    if getattr(ahat, "dim", lambda: 0)() != 4:
+        raise ValueError(f"ahat: shape {tuple(getattr(ahat, 'shape', ()))}, expected (nkeys, k, l, n)")
+    nkeys = ahat.shape[0]
+    if not 1 <= nkeys <= MUL_KEYS_MAX or tuple(ahat.shape[2:]) != (len(ys), n):
+        raise ValueError(f"ahat: shape {tuple(ahat.shape)}, expected (nkeys >= 1, k, l = {len(ys)}, n = {n})")
+    if not ahat.is_contiguous():
+        raise ValueError("ahat: tensor must be contiguous ([nkeys][k][l][n])")
+    if keys is not None:   # shapes before devices, as _rows_operands
+        if keys.dtype != torch.int32:
+            raise ValueError(f"keys: dtype {keys.dtype}, expected int32")
+        if keys.dim() != 1 or not ys or keys.shape[0] != ys[0].numel() // n:
+            raise ValueError(f"keys: shape {tuple(keys.shape)}, expected [batch]")
+    py, pa, nb, k, l, tensors = _rows_operands(n, ys, ahat[0], add, out)
+    pk = None
+    if keys is not None:
+        _batch(keys, 1)   # device, contiguity
+        tensors, pk = (*tensors, keys), keys.data_ptr()
+    return py, pa, nb, k, l, tensors, pk, nkeys
+
+
+def poly_mul_ntt_kl_keyed(out, ys, ahat, keys, param_set, add=None, stream=None):
+    """poly_mul_ntt_kl over many keys in one launch: message b is multiplied
+    by the rows of key min(keys[b], nkeys - 1), or of key min(b, nkeys - 1) with
+    keys None (a key-generation batch's t_b = a_b s_b + e_b with one ys, one a
+    per key).  ahat is a contiguous int32 (nkeys, k, l, n) tensor, key j's
+    block what poly_mul_ntt_kl takes -- poly_gen_a over nkeys seeds writes all
+    of it (l = 1), or slot 0 of every key with pstride = 2 n (l = 2); keys is an
+    int32 [batch] tensor on the same device (read as unsigned: an index beyond
+    the last key, a caller's bug, gives the last key's result) or None.  ys,
+    add and out as poly_mul_ntt_kl.  Returns out."""
+    py, pa, nb, k, l, tensors, pk, nkeys = _keyed_operands(_n(param_set), ys, ahat, keys, add, out)
+    fn = lib().poly_mul_ntt_kl_keyed
+    _run("poly_mul_ntt_kl_keyed", tensors, stream,
+         lambda s: fn(out.data_ptr(), py, ahat.data_ptr(), pk, nkeys, pa, nb, k, l, _ps(param_set), s))
+    return out
+
+
+def poly_mul_ntt_kl_round_keyed(ys, ahat, keys, param_set, d: int, hi=None, norms=None, add=None, stream=None):
+    """poly_mul_ntt_kl_round over many keys in one launch (a batch of
+    signatures made under different public keys, verified together): ahat and
+    keys as poly_mul_ntt_kl_keyed, everything else as poly_mul_ntt_kl_round.
+    Returns (hi, norms)."""
+    n = _n(param_set)
+    py, pa, nb, k, l, ins, pk, nkeys = _keyed_operands(n, ys, ahat, keys, add)
+    outs = _round_outputs("poly_mul_ntt_kl_round_keyed", hi, norms, nb * k, n, d)
+    fn = lib().poly_mul_ntt_kl_round_keyed
+    ph = None if hi is None else hi.data_ptr()
+    pn = None if norms is None else norms.data_ptr()
+    _run("poly_mul_ntt_kl_round_keyed", (*ins, *outs), stream,
+         lambda s: fn(ph, pn, py, ahat.data_ptr(), pk, nkeys, pa, nb, k, l, int(d), _ps(param_set), s))
     return hi, norms
 
 
