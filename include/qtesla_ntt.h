@@ -438,6 +438,85 @@ int poly_sample_y(uint32_t *d_y, const uint8_t *d_seed, size_t seedlen,
 int poly_gen_a(uint32_t *d_a, size_t pstride, const uint8_t *d_seed, size_t seedlen,
                size_t batch, int k, int nblocks, int param_set, void *stream);
 
+/* qTESLA's Gaussian sampler: one seed and a nonce to the n coefficients of a
+ * secret polynomial (s, e_1 .. e_k), each a constant-time count over a
+ * cumulative distribution table -- key generation's first step, so that no
+ * secret coefficient is ever produced on the host.
+ *   d_out   [batch][n] uint32, every word written once
+ *   d_seed  [batch][seedlen] bytes, one seed per polynomial
+ *   d_nonce NULL, or [batch] uint32: one restart counter per polynomial
+ *   d_cdt   [rows][cols] uint32, the table, most significant limb first; only
+ *           the low 31 bits of a word are used
+ * Polynomial b uses nonce_b = ((d_nonce ? d_nonce[b] : 0) + nonce) & 0xFF,
+ * exactly as poly_sample_y.  The table is the caller's (the library keeps no
+ * scheme constants), as is the hash; n and q are param_set's.  Row j is the
+ * integer
+ *   T_j = sum_k (cdt[j][k] & 0x7FFFFFFF) * 2^(31 (cols - 1 - k))
+ * and every row is compared: a qTESLA caller passes its table from row 1 on,
+ * because upstream's row 0 is zero and skipped.  A polynomial is n / 512
+ * chunks (n is a multiple of 512 in all five parameter sets, at most 16
+ * chunks), each chunk a cSHAKE call of its own with ntt_xof's cshake*_simple
+ * (sample_gauss_poly of qTESLA round 2, restated from memory; this statement,
+ * not the upstream file, is what the tests bind):
+ *   for ch in 0 .. n / 512 - 1:
+ *       buf = cshake_simple(algo, seed_b, outlen = 512 * cols * 4,
+ *                           cstm = ((nonce_b << 8) + ch) & 0xFFFF)
+ *       for i in 0 .. 511:
+ *           W_k  = le32(buf + 4 * (i * cols + k))            for k < cols
+ *           R    = sum_k (W_k & 0x7FFFFFFF) * 2^(31 (cols - 1 - k))
+ *           m    = #{ j < rows : R >= T_j }
+ *           sign = W_0 >> 31
+ *           out[b][512 * ch + i] = (sign && m) ? q - m : m
+ * The value is canonical in [0, q): "-0" is 0, never q.  There is no
+ * rejection and no refill: the stream positions of every sample are fixed.
+ * Constant time: the outputs and their source words are secret.  On the
+ * device no branch, loop bound, memory address or LDS address depends on R, m
+ * or sign; the count always runs over all `rows` rows, and a comparison is a
+ * flag, not a jump.  (This rule is kept by construction and verified by
+ * reading csrc/ntt_gauss.hpp; no test can observe it.)
+ * 1 <= rows <= NTT_GAUSS_ROWS_MAX, 1 <= cols <= NTT_GAUSS_COLS_MAX (qTESLA:
+ * cols 2 for p-I, 4 for p-III); algo is NTT_XOF_SHAKE128 or NTT_XOF_SHAKE256.
+ * All five parameter sets.  Checks, in this order (the first defect decides):
+ *   NTT_ERR_PARAM  param_set; algo; rows outside 1 .. 128; cols outside 1 .. 4;
+ *                  nonce > 255; seedlen not a multiple of 8 or outside
+ *                  8 .. rate - 8 (one absorb block: 160 / 128)
+ *   batch == 0     NTT_OK, nothing else is looked at
+ *   NTT_ERR_NULL   d_out, d_seed, d_cdt
+ *   NTT_ERR_ALIGN  d_out 16-byte, d_seed 8-byte, d_cdt 4-byte, d_nonce 4-byte
+ *                  when not NULL
+ *   NTT_ERR_SIZE   batch > 2^31 - 1
+ *   NTT_ERR_ALIAS  d_out overlaps the seeds, the nonces or the table
+ * One chunk per lane: a batch gives batch * n / 512 lanes, and the throughput
+ * comes from the batch. */
+#define NTT_GAUSS_CHUNK 512
+#define NTT_GAUSS_ROWS_MAX 128
+#define NTT_GAUSS_COLS_MAX 4
+int poly_sample_gauss(uint32_t *d_out, const uint8_t *d_seed, size_t seedlen,
+                      const uint32_t *d_nonce, uint32_t nonce,
+                      const uint32_t *d_cdt, int rows, int cols,
+                      size_t batch, int algo, int param_set, void *stream);
+
+/* qTESLA's check_ES: the sum of the h largest |coefficients| of a polynomial,
+ * which key generation compares with L_S / L_E and which bounds |s c| and
+ * |e c| in the signer's tests.
+ *   d_w   [batch][n] uint32, entries < 2q
+ *   d_sum [batch] uint64
+ * With c_i the centred value of coefficient i exactly as poly_round defines
+ * it (x' = x mod q, c = x' - q if x' > (q-1)/2, else x'), d_sum[b] is the sum
+ * of the h largest |c_i| of polynomial b; equal values are counted as often
+ * as they occur (the sum of the first h entries of |c| sorted downwards).
+ * The output is 64-bit because h (q-1)/2 exceeds 32 bits.  1 <= h <= n.  The
+ * input is secret: control flow and addresses do not depend on it.
+ * All five parameter sets.  Checks, in this order (the first defect decides):
+ *   NTT_ERR_PARAM  param_set; h outside 1 .. n
+ *   batch == 0     NTT_OK, nothing else is looked at
+ *   NTT_ERR_NULL   d_sum, d_w
+ *   NTT_ERR_ALIGN  d_w 16-byte, d_sum 8-byte
+ *   NTT_ERR_SIZE   batch > 2^31 - 1
+ *   NTT_ERR_ALIAS  d_sum overlaps d_w */
+int poly_hsum(uint64_t *d_sum, const uint32_t *d_w, size_t batch, int h,
+              int param_set, void *stream);
+
 /* qTESLA's wire formats: coefficients to bit-packed rows and back -- a
  * signature's z as n fields of B_BITS + 1 bits (p-I: 20, p-III: 22), a public
  * key's t as k n fields of ceil(log2 q) bits (29 / 30) -- so that signature

@@ -23,6 +23,7 @@
 #include "ntt_mulkl.hpp"
 #include "ntt_pack.hpp"
 #include "ntt_round.hpp"
+#include "ntt_gauss.hpp"
 #include "ntt_gen_a.hpp"
 #include "ntt_sample.hpp"
 #include "ntt_xof.hpp"
@@ -589,6 +590,25 @@ int mul_kl_round_common(uint8_t *d_hi, uint32_t *d_norms, const RowOps &in, bool
     return launch<LMulKLRound, LARGE_PS0>(ps, in.y, in.l, in.ahat, in.add, ro, batch, k, (hipStream_t)stream);
 }
 
+// k_sample_gauss<R, C> for the run-time rate and 1 <= cols <= NTT_GAUSS_COLS_MAX
+template <int R, int C = 1, class... Args> void launch_gauss(int cols, dim3 grid, hipStream_t s, Args... args)
+{
+    if constexpr (C <= NTT_GAUSS_COLS_MAX) {
+        if (cols == C) hipLaunchKernelGGL((k_sample_gauss<R, C>), grid, dim3(GAUSS_WG), 0, s, args...);
+        else launch_gauss<R, C + 1>(cols, grid, s, args...);
+    }
+}
+
+// poly_hsum (ntt_gauss.hpp): a wave per polynomial, HSUM_WAVES of them a workgroup
+template <int PS> struct LHsum {
+    static int run(uint64_t *sum, const uint32_t *w, size_t batch, int h, hipStream_t s, const DevInfo &)
+    {
+        hipLaunchKernelGGL(k_hsum<PS>, dim3((uint32_t)ceil_div(batch, (size_t)HSUM_WAVES)), dim3(HSUM_WAVES * 64), 0, s, sum, w,
+                           (uint32_t)batch, (uint32_t)h);
+        return finish_launch();
+    }
+};
+
 }  // namespace
 
 void set_last_hip(int e) { t_last_hip = e; }
@@ -881,6 +901,51 @@ int poly_gen_a(uint32_t *d_a, size_t pstride, const uint8_t *d_seed, size_t seed
                        pstride, (const uint64_t *)d_seed, (uint32_t)(seedlen / 8), (uint32_t)batch, (uint32_t)k, p->logn, p->q,
                        (uint32_t)((1ull << qbits) - 1), (uint32_t)nblocks, (uint32_t)(refills < 65535 ? refills : 65535));
     return finish_launch();
+}
+
+int poly_sample_gauss(uint32_t *d_out, const uint8_t *d_seed, size_t seedlen, const uint32_t *d_nonce, uint32_t nonce,
+                      const uint32_t *d_cdt, int rows, int cols, size_t batch, int algo, int ps, void *stream)
+{
+    static_assert(GAUSS_CHUNK == NTT_GAUSS_CHUNK, "the header's chunk");
+    const ParamSet *p = param_set(ps);
+    if (!p || (algo != NTT_XOF_SHAKE128 && algo != NTT_XOF_SHAKE256)) return NTT_ERR_PARAM;
+    const size_t rate = algo == NTT_XOF_SHAKE128 ? 8 * XOF_RATE128 : 8 * XOF_RATE256;
+    if (rows < 1 || rows > NTT_GAUSS_ROWS_MAX || cols < 1 || cols > NTT_GAUSS_COLS_MAX || nonce > 255) return NTT_ERR_PARAM;
+    if ((seedlen & 7u) || seedlen < 8 || seedlen > rate - 8) return NTT_ERR_PARAM;   // one absorb block
+    if (batch == 0) return NTT_OK;
+    if (!d_out || !d_seed || !d_cdt) return NTT_ERR_NULL;
+    if ((((uintptr_t)d_out) & 15u) || (((uintptr_t)d_seed) & 7u) || (((uintptr_t)d_cdt) & 3u) || (((uintptr_t)d_nonce) & 3u))
+        return NTT_ERR_ALIGN;
+    if (batch > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
+    const size_t obytes = batch * p->n * 4;
+    if (ranges_overlap(d_out, obytes, d_seed, batch * seedlen) || (d_nonce && ranges_overlap(d_out, obytes, d_nonce, batch * 4)) ||
+        ranges_overlap(d_out, obytes, d_cdt, (size_t)rows * cols * 4))
+        return NTT_ERR_ALIAS;
+    int rc;
+    DevInfo *d = nullptr;
+    if ((rc = device_ready(&d)) != NTT_OK) return rc;
+    const uint32_t lcpp = p->logn - 9;   // n / 512 chunks a polynomial
+    const dim3 grid((uint32_t)ceil_div(batch << lcpp, (size_t)GAUSS_WG));
+    const uint32_t sw = (uint32_t)(seedlen / 8);
+    if (algo == NTT_XOF_SHAKE128)
+        launch_gauss<XOF_RATE128>(cols, grid, (hipStream_t)stream, d_out, (const uint64_t *)d_seed, sw, d_nonce, nonce, d_cdt,
+                                  (uint32_t)rows, (uint32_t)batch, lcpp, p->q);
+    else
+        launch_gauss<XOF_RATE256>(cols, grid, (hipStream_t)stream, d_out, (const uint64_t *)d_seed, sw, d_nonce, nonce, d_cdt,
+                                  (uint32_t)rows, (uint32_t)batch, lcpp, p->q);
+    return finish_launch();
+}
+
+int poly_hsum(uint64_t *d_sum, const uint32_t *d_w, size_t batch, int h, int ps, void *stream)
+{
+    const ParamSet *p = param_set(ps);
+    if (!p || h < 1 || (uint32_t)h > p->n) return NTT_ERR_PARAM;
+    if (batch == 0) return NTT_OK;
+    if (!d_sum || !d_w) return NTT_ERR_NULL;
+    if ((((uintptr_t)d_w) & 15u) || (((uintptr_t)d_sum) & 7u)) return NTT_ERR_ALIGN;
+    if (batch > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
+    if (ranges_overlap(d_sum, batch * 8, d_w, batch * p->n * 4)) return NTT_ERR_ALIAS;
+    return launch<LHsum>(ps, d_sum, d_w, batch, h, (hipStream_t)stream);
 }
 
 int poly_pack(uint8_t *d_out, size_t stride, const uint32_t *d_w, size_t batch, int k, int bits, int sgn, int ps, void *stream)

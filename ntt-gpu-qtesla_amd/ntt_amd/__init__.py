@@ -100,6 +100,9 @@ def lib():
         L.poly_challenge.argtypes = [_vp, _vp, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_sample_y.argtypes = [_vp, _vp, _sz, _vp, ctypes.c_uint32, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_gen_a.argtypes = [_vp, _sz, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
+        L.poly_sample_gauss.argtypes = [_vp, _vp, _sz, _vp, ctypes.c_uint32, _vp, ctypes.c_int, ctypes.c_int, _sz, ctypes.c_int,
+                                        ctypes.c_int, _vp]
+        L.poly_hsum.argtypes = [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_pack.argtypes = [_vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_unpack.argtypes = [_vp, _vp, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_mul_nussbaumer.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
@@ -645,6 +648,9 @@ XOF_OUT_MAX = 512          # NTT_XOF_OUT_MAX
 CHALLENGE_H_MAX = 128      # NTT_CHALLENGE_H_MAX
 SAMPLE_Y_REFILLS_MAX = 255   # NTT_SAMPLE_Y_REFILLS_MAX
 GEN_A_BLOCKS_MAX = 256       # NTT_GEN_A_BLOCKS_MAX
+GAUSS_CHUNK = 512            # NTT_GAUSS_CHUNK
+GAUSS_ROWS_MAX = 128         # NTT_GAUSS_ROWS_MAX
+GAUSS_COLS_MAX = 4           # NTT_GAUSS_COLS_MAX
 
 
 def _byte_rows(name: str, t, batch: int) -> int:
@@ -781,6 +787,62 @@ def poly_gen_a(a, seed, param_set, nblocks: int, k: int, pstride=None, stream=No
     _run("poly_gen_a", (a, seed), stream,
          lambda s: fn(a.data_ptr(), pstride, seed.data_ptr(), seedlen, nb, int(k), int(nblocks), _ps(param_set), s))
     return a
+
+
+def poly_sample_gauss(out, seed, cdt, param_set, algo="shake256", nonce: int = 0, nonces=None, stream=None):
+    """qTESLA's CDT Gaussian sampler: seed [batch, seedlen] int8/uint8 (seedlen a
+    multiple of 8 within 8 .. 160 for SHAKE128, 8 .. 128 for SHAKE256), one
+    seed per polynomial, to the secret polynomials out, int32 [batch, n] (or
+    flat), canonical in [0, q).  cdt is the caller's cumulative table, an int32
+    device tensor [rows, cols] with 1 <= rows <= 128 and 1 <= cols <= 4, most
+    significant 31-bit limb first; a coefficient is +-#{rows <= the sample}.
+    Polynomial b is drawn at nonce (nonces[b] + nonce) & 0xFF: nonce a scalar
+    0 .. 255, nonces None or an int32 [batch] device tensor of per-polynomial
+    restart counters.  Returns out."""
+    nb = _batch(out, _n(param_set))
+    if out.dim() > 1 and out.shape[0] != nb:
+        raise ValueError(f"out: shape {tuple(out.shape)}, expected [{nb}, n] or flat")
+    _batch(cdt, 1)   # device, dtype, contiguity
+    if cdt.dim() != 2 or not 1 <= cdt.shape[0] <= GAUSS_ROWS_MAX or not 1 <= cdt.shape[1] <= GAUSS_COLS_MAX:
+        raise ValueError(f"cdt: shape {tuple(cdt.shape)}, expected [1 .. {GAUSS_ROWS_MAX}, 1 .. {GAUSS_COLS_MAX}]")
+    rows, cols = cdt.shape
+    if not 0 <= int(nonce) <= 255:
+        raise ValueError(f"nonce = {nonce}, expected 0 .. 255")
+    if isinstance(algo, str) and algo not in XOF_ALGOS:
+        raise ValueError(f"algo {algo!r}, expected one of {sorted(XOF_ALGOS)}")
+    a = XOF_ALGOS[algo] if isinstance(algo, str) else int(algo)
+    seedlen = _byte_rows("seed", seed, nb)
+    smax = 128 if a == XOF_ALGOS["shake256"] else 160
+    if seed.dim() != 2 or not 8 <= seedlen <= smax:
+        raise ValueError(f"seed: shape {tuple(seed.shape)}, expected [{nb}, 8 .. {smax}]")
+    tensors = (out, seed, cdt)
+    pn = None
+    if nonces is not None:
+        if _batch(nonces, 1) != nb or nonces.dim() != 1:
+            raise ValueError(f"nonces: shape {tuple(nonces.shape)}, expected [{nb}]")
+        tensors, pn = (out, seed, cdt, nonces), nonces.data_ptr()
+    fn = lib().poly_sample_gauss
+    _run("poly_sample_gauss", tensors, stream,
+         lambda s: fn(out.data_ptr(), seed.data_ptr(), seedlen, pn, int(nonce), cdt.data_ptr(), rows, cols, nb, a,
+                      _ps(param_set), s))
+    return out
+
+
+def poly_hsum(sums, w, param_set, h: int, stream=None):
+    """qTESLA's check_ES: sums[b] = the sum of the h largest |c| of polynomial
+    b of w, int32 [batch, n] (or flat; entries < 2q, c the centred value as in
+    poly_round), equal values counted as often as they occur.  sums is an
+    int64 device tensor of batch elements; 1 <= h <= n.  Returns sums."""
+    torch = _torch()
+    n = _n(param_set)
+    nb = _batch(w, n)
+    if _batch(sums, 1, (torch.int64,), "int64") != nb:
+        raise ValueError(f"sums: numel {sums.numel()} is not the batch {nb}")
+    if not 1 <= int(h) <= n:
+        raise ValueError(f"h = {h}, expected 1 .. {n}")
+    fn = lib().poly_hsum
+    _run("poly_hsum", (sums, w), stream, lambda s: fn(sums.data_ptr(), w.data_ptr(), nb, int(h), _ps(param_set), s))
+    return sums
 
 
 def _pack_operands(rows, w, param_set, bits, signed, maxima=None):
