@@ -576,6 +576,58 @@ int poly_pack(uint8_t *d_out, size_t stride, const uint32_t *d_w, size_t batch,
 int poly_unpack(uint32_t *d_w, uint32_t *d_max /* [batch][k] or NULL */, const uint8_t *d_in,
                 size_t stride, size_t batch, int k, int bits, int sgn, int param_set, void *stream);
 
+/* Packed rows straight to NTT-domain polynomials, one launch: poly_unpack,
+ * poly_ntt and, with neg, the entrywise negation, without the two full-width
+ * temporaries between them -- a public key's t to slot 1 of the verification
+ * rows (q - t-hat), a signer's s and e_i from its key bytes to s-hat and
+ * q - e-hat_i.
+ *   Byte side.  Exactly poly_unpack's: rows `stride` bytes apart, k
+ *     polynomials of n b / 8 bytes back to back, the bit stream, the field
+ *     layout and sgn as defined there.  Bytes [k n b / 8, stride) of a row are
+ *     never read.
+ *   Value.  Let x be the canonical polynomial poly_unpack gives for a
+ *     polynomial's bytes and X = poly_ntt(x): natural order, this library's
+ *     psi.  The result is X when neg = 0 and (q - X) mod q entrywise when
+ *     neg = 1, so 0 stays 0.  Either way it is canonical, in [0, q), and
+ *     bit-identical to poly_unpack into a temporary followed by poly_ntt
+ *     (neg = 1: followed by the entrywise negation mod q).
+ *   Placement.  Polynomial i of row r is written to words
+ *     [(r k + i) pstride, (r k + i) pstride + n) of d_out, every one of them
+ *     once by a plain vector store; the pstride - n words after a polynomial
+ *     are never written.  pstride = n is dense [batch][k][n]; pstride = 2n with
+ *     d_out = d_at + n fills slot 1 of [nkeys][k][2][n] verification rows in
+ *     place, beside poly_gen_a's slot 0.
+ *   Maxima.  d_max is poly_unpack's, NULL or [batch][k] uint32: signed fields
+ *     give max |s|, unsigned fields the largest raw field, so a malformed key
+ *     shows as a maximum >= q.  With d_max NULL nothing is computed for it.
+ *   Secret input.  With sgn = 1 the bytes may be a signer's key.  On the
+ *     device no branch, loop bound, global or LDS address depends on a field's
+ *     value: addresses are functions of the lane, the register index, b and the
+ *     polynomial's index; sign extension, reduction and maximum are selects.
+ *     (Kept by construction and verified by reading csrc/ntt_unpack_ntt.hpp;
+ *     no test can observe it.)
+ * Parameter sets: ref, p-I, p-III (n = 1024 / 2048, as for poly_mul_ntt_k).
+ * One kernel and one launch serve every batch size.  Asynchronous on `stream`.
+ * Checks, in this order (the first defect decides; all of them run before any
+ * GPU work):
+ *   NTT_ERR_PARAM  param_set (unknown, or n > 2048); k outside
+ *                  1 .. NTT_MUL_K_MAX; sgn or neg not 0 or 1; bits outside
+ *                  poly_unpack's range for that sgn; stride not a multiple of
+ *                  16 or < k n bits / 8; pstride < n or not a multiple of 4
+ *   batch == 0     NTT_OK, nothing else is looked at
+ *   NTT_ERR_NULL   d_out, d_in (d_max may be NULL)
+ *   NTT_ERR_ALIGN  d_out and d_in 16-byte, d_max 4-byte when not NULL
+ *   NTT_ERR_SIZE   batch * k > 2^31 - 1
+ *   NTT_ERR_ALIAS  d_out's extent, ((batch k - 1) pstride + n) words, overlaps
+ *                  the byte side's extent, (batch - 1) stride + k n bits / 8;
+ *                  or d_max's batch k words overlap either.  Only extents are
+ *                  compared: an output that lies in the gaps of another
+ *                  pstride-strided buffer overlaps that buffer's extent, which
+ *                  is not an operand and is not looked at. */
+int poly_unpack_ntt(uint32_t *d_out, size_t pstride, uint32_t *d_max /* [batch][k] or NULL */,
+                    const uint8_t *d_in, size_t stride, size_t batch, int k, int bits, int sgn,
+                    int neg, int param_set, void *stream);
+
 /* Nussbaumer negacyclic product (the paper's alternate algorithm): the
  * reference's single-polynomial CPU routine nussbaumer_fft (NTT.cu:167-277,
  * driver test_nussbaumer :1987-2005), batched on the GPU and extended from

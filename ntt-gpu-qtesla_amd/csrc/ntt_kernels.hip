@@ -26,6 +26,7 @@
 #include "ntt_gauss.hpp"
 #include "ntt_gen_a.hpp"
 #include "ntt_sample.hpp"
+#include "ntt_unpack_ntt.hpp"
 #include "ntt_xof.hpp"
 #include "ntt_internal.h"
 #include "params.hpp"
@@ -528,6 +529,20 @@ int pack_common(const void *bytes, const void *w, const void *mx, bool unpack, s
     return launch<LPack>(ps, (uint32_t *)bytes, (uint32_t *)w, (uint32_t *)mx, unpack, R, batch * k, (hipStream_t)stream);
 }
 
+// poly_unpack_ntt (ntt_unpack_ntt.hpp): k_ntt_fwd's workgroup and launch shape, one kernel for every batch
+template <int PS> struct LUnpackNtt {
+    static int run(uint32_t *out, size_t pstride, uint32_t *mx, const uint32_t *bytes, const PackRows &R, bool neg, size_t npoly,
+                   hipStream_t s, const DevInfo &d)
+    {
+        const LaunchShape l = batch_shape<PS>(npoly, NTT_WG / 64, d);
+        with_flag(mx != nullptr, [&](auto m) {
+            hipLaunchKernelGGL((k_unpack_ntt<PS, decltype(m)::value>), dim3(l.grid), dim3(NTT_WG), 0, s, out, pstride, mx, bytes, R,
+                               neg ? 1u : 0u, (uint32_t)npoly, l.chunk);
+        });
+        return finish_launch();
+    }
+};
+
 // largest hi of poly_round: it fits a signed byte iff this is <= 127
 uint32_t round_hmax(uint32_t q, int d) { return ((q - 1) / 2 + (1u << (d - 1)) - 1) >> d; }
 
@@ -957,6 +972,30 @@ int poly_unpack(uint32_t *d_w, uint32_t *d_max, const uint8_t *d_in, size_t stri
                 int ps, void *stream)
 {
     return pack_common(d_in, d_w, d_max, true, stride, batch, k, bits, sgn, ps, stream);
+}
+
+int poly_unpack_ntt(uint32_t *d_out, size_t pstride, uint32_t *d_max, const uint8_t *d_in, size_t stride, size_t batch, int k,
+                    int bits, int sgn, int neg, int ps, void *stream)
+{
+    const ParamSet *p = row_param_set(ps, k, 1);   // n <= 2048, k
+    if (!p || (sgn != 0 && sgn != 1) || (neg != 0 && neg != 1)) return NTT_ERR_PARAM;
+    int qbits = 0;
+    while (p->q >> qbits) ++qbits;
+    if (bits < 8 || bits > qbits - sgn) return NTT_ERR_PARAM;
+    const size_t packed = (size_t)k * p->n * (size_t)bits / 8;
+    if ((stride & 15u) || stride < packed) return NTT_ERR_PARAM;
+    if (pstride < p->n || (pstride & 3u)) return NTT_ERR_PARAM;
+    if (batch == 0) return NTT_OK;
+    if (!d_out || !d_in) return NTT_ERR_NULL;
+    if ((((uintptr_t)d_out) | ((uintptr_t)d_in)) & 15u || (((uintptr_t)d_max) & 3u)) return NTT_ERR_ALIGN;
+    if (batch > (size_t)0x7FFFFFFF / (size_t)k) return NTT_ERR_SIZE;
+    const size_t bbytes = (batch - 1) * stride + packed, obytes = ((batch * k - 1) * pstride + p->n) * 4, mbytes = batch * k * 4;
+    if (ranges_overlap(d_out, obytes, d_in, bbytes)) return NTT_ERR_ALIAS;
+    if (d_max && (ranges_overlap(d_max, mbytes, d_in, bbytes) || ranges_overlap(d_max, mbytes, d_out, obytes))) return NTT_ERR_ALIAS;
+    const PackRows R = {stride, (uint32_t)k, (uint32_t)bits, sgn ? 1u << (bits - 1) : 0u, p->q,
+                        (uint32_t)(((uint64_t)1 << 32) / (uint32_t)bits) + 1u};
+    return launch<LUnpackNtt, LARGE_PS0>(ps, d_out, pstride, d_max, (const uint32_t *)d_in, R, neg != 0, batch * k,
+                                         (hipStream_t)stream);
 }
 
 int poly_mul_nussbaumer(uint32_t *d_c, const uint32_t *d_a, const uint32_t *d_b, size_t batch, int ps, int ring,

@@ -105,6 +105,8 @@ def lib():
         L.poly_hsum.argtypes = [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_pack.argtypes = [_vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_unpack.argtypes = [_vp, _vp, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
+        L.poly_unpack_ntt.argtypes = [_vp, _sz, _vp, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_int, _vp]
         L.poly_mul_nussbaumer.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.ntt_fill_uniform.argtypes = [_vp, _sz, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, _vp]
         L.ntt_last_hip_error.restype = ctypes.c_int
@@ -906,6 +908,56 @@ def poly_unpack(w, inp, param_set, bits: int, signed=True, maxima=None, stream=N
     _run("poly_unpack", tensors, stream,
          lambda s: fn(w.data_ptr(), pm, inp.data_ptr(), stride, nb, k, int(bits), sgn, _ps(param_set), s))
     return w, maxima
+
+
+def poly_unpack_ntt(out, inp, param_set, bits: int, k: int, signed=False, negate=False, pstride=None, maxima=None,
+                    stream=None):
+    """poly_unpack, poly_ntt and (negate) the entrywise negation mod q in one
+    launch: the rows inp, int8/uint8 [batch, stride] with k polynomials of
+    n*bits/8 bytes each, to canonical NTT-domain polynomials in natural order.
+    out is a flat (or any contiguous) int32 device tensor; polynomial i of row
+    b starts at element (b*k + i)*pstride and the pstride - n elements after it
+    are not written.  out has batch*k*pstride elements, or ends with its last
+    polynomial: (batch*k - 1)*pstride + n elements, which is what a view from
+    an offset into a larger buffer has.  pstride defaults to n (dense
+    [batch, k, n]); pstride = 2n with out = rows.view(-1)[n:] fills slot 1 of
+    [batch, k, 2, n] verification rows in place, beside poly_gen_a's slot 0
+    (negate=True: q - t-hat).  maxima is poly_unpack's: None or int32 with
+    batch*k elements.  Parameter sets "ref", "p-I", "p-III".  Returns
+    (out, maxima)."""
+    torch = _torch()
+    info = param_info(param_set)
+    n, qbits = info["n"], info["q"].bit_length()
+    _batch(inp, 1, (torch.int8, torch.uint8), "int8/uint8")   # device, dtype, contiguity
+    if inp.dim() != 2:
+        raise ValueError(f"inp: shape {tuple(inp.shape)}, expected [batch, stride]")
+    nb, stride = inp.shape
+    _batch(out, 1)
+    if not 1 <= int(k) <= MUL_K_MAX:
+        raise ValueError(f"k = {k}, expected 1 .. {MUL_K_MAX}")
+    k = int(k)
+    sgn = 1 if signed else 0
+    if not 8 <= int(bits) <= qbits - sgn:
+        raise ValueError(f"bits = {bits}, expected 8 .. {qbits - sgn} ({'signed' if sgn else 'unsigned'})")
+    packed = k * n * int(bits) // 8
+    if stride % 16 or stride < packed:
+        raise ValueError(f"inp: stride {stride}, expected a multiple of 16 and >= k*n*bits/8 = {packed}")
+    pstride = n if pstride is None else int(pstride)
+    if pstride < n or pstride % 4:
+        raise ValueError(f"pstride = {pstride}, expected a multiple of 4 and >= n = {n}")
+    if nb and out.numel() not in (nb * k * pstride, (nb * k - 1) * pstride + n):
+        raise ValueError(f"out: numel {out.numel()} is neither batch*k*pstride = {nb}*{k}*{pstride} "
+                         f"nor (batch*k - 1)*pstride + n")
+    tensors, pm = (out, inp), None
+    if maxima is not None:
+        if _batch(maxima, 1) != nb * k:
+            raise ValueError(f"maxima: numel {maxima.numel()} is not batch*k = {nb}*{k}")
+        tensors, pm = (out, inp, maxima), maxima.data_ptr()
+    fn = lib().poly_unpack_ntt
+    _run("poly_unpack_ntt", tensors, stream,
+         lambda s: fn(out.data_ptr(), pstride, pm, inp.data_ptr(), stride, nb, k, int(bits), sgn, 1 if negate else 0,
+                      _ps(param_set), s))
+    return out, maxima
 
 
 def poly_mul_nussbaumer(c, a, b, param_set, ring="q", stream=None):
