@@ -311,6 +311,55 @@ int poly_mul_ntt_kl_round_keyed(uint8_t *d_hi, uint32_t *d_norms, const uint32_t
 int ntt_xof(uint8_t *d_out, size_t outlen, const uint8_t *d_in0, size_t len0,
             const uint8_t *d_in1, size_t len1, size_t batch, int algo, int cstm, void *stream);
 
+/* ntt_xof's hash over messages of any byte length, each its own, one launch --
+ * qTESLA's G(m), the 64-byte digest of every message of a batch, from the
+ * messages as they arrive:
+ *   d_msg [msg_bytes] bytes    all messages back to back (CSR style)
+ *   d_off [batch + 1] uint64   their byte offsets, in device memory
+ *   d_out [batch][outlen]
+ * Message b is d_msg[begin_b .. end_b) with
+ *   begin_b = min(d_off[b], msg_bytes)
+ *   end_b   = min(max(d_off[b + 1], begin_b), msg_bytes)
+ * The minimum and the maximum are the definition, not an error path (the
+ * device cannot return an error; poly_mul_ntt_kl_keyed treats its key index the
+ * same way): no offset makes the kernel read outside d_msg.  For a well-formed
+ * table -- non-decreasing, ending at or below msg_bytes -- message b is simply
+ * [d_off[b], d_off[b + 1]).  Any length is legal, 0 included, and a message
+ * may start at any byte.  Offsets and lengths are 64-bit throughout.
+ *   algo, cstm, outlen   exactly ntt_xof's: NTT_XOF_SHAKE128 / NTT_XOF_SHAKE256;
+ *          cstm -1 plain SHAKE (domain byte 0x1F), 0 .. 65535 cshake*_simple
+ *          (the prefix block, one permutation, then domain byte 0x04); outlen a
+ *          multiple of 8 with 8 <= outlen <= NTT_XOF_OUT_MAX.
+ * Padding, with L = end_b - begin_b and r = L mod rate: the full rate blocks
+ * are absorbed; the last block gets the r remaining bytes, the domain byte at
+ * byte r and 0x80 at byte rate - 1.  For r = rate - 1 both land on the same
+ * byte (0x9F for SHAKE, 0x84 for cSHAKE); for r = 0 the last block is padding
+ * only.
+ * Read range: msg_bytes is a multiple of 8 -- the caller pads the buffer --
+ * and d_msg is 8-byte aligned.  The kernel reads d_msg only in aligned 8-byte
+ * words that contain at least one byte of some message's [begin_b, end_b), so
+ * never outside [d_msg, d_msg + msg_bytes); bytes that are not message b's never
+ * influence d_out[b].  msg_bytes == 0 is legal: every message is then empty and
+ * d_msg is not looked at (it may be NULL, misaligned, anywhere).
+ * Checks, in this order (the first defect decides; all before any GPU work):
+ *   NTT_ERR_PARAM  unknown algo, cstm outside -1 .. 65535, a bad outlen,
+ *                  msg_bytes not a multiple of 8
+ *   batch == 0     NTT_OK, nothing else is looked at
+ *   NTT_ERR_NULL   d_out, d_off, or d_msg with msg_bytes > 0
+ *   NTT_ERR_ALIGN  any of the three pointers not 8-byte aligned (d_msg counts
+ *                  only with msg_bytes > 0)
+ *   NTT_ERR_SIZE   batch > 2^31 - 1
+ *   NTT_ERR_ALIAS  d_out's batch * outlen bytes overlap d_msg's msg_bytes or
+ *                  d_off's 8 (batch + 1) bytes (the two inputs may overlap each
+ *                  other)
+ * One message per lane, one launch for every batch size.  A wave of 64
+ * consecutive messages costs its longest message's serial chain of
+ * permutations: a caller with very uneven lengths should sort or bucket the
+ * messages by length.  There is no cooperative path for one huge message, and
+ * a small batch is as slow as ntt_xof's: the throughput comes from the batch. */
+int ntt_xof_ragged(uint8_t *d_out, size_t outlen, const uint8_t *d_msg, size_t msg_bytes,
+                   const uint64_t *d_off, size_t batch, int algo, int cstm, void *stream);
+
 /* qTESLA's Enc(c'): a seed to the h positions and signs of the challenge,
  * exactly the lists poly_scatter takes.
  *   d_seed [batch][seedlen] bytes; d_pos, d_val [batch][h] uint32

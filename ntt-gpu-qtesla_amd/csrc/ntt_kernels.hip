@@ -28,6 +28,7 @@
 #include "ntt_sample.hpp"
 #include "ntt_unpack_ntt.hpp"
 #include "ntt_xof.hpp"
+#include "ntt_xof_ragged.hpp"
 #include "ntt_internal.h"
 #include "params.hpp"
 #include "pset.hpp"
@@ -834,6 +835,34 @@ int ntt_xof(uint8_t *d_out, size_t outlen, const uint8_t *d_in0, size_t len0, co
     else
         hipLaunchKernelGGL(k_xof<XOF_RATE256>, grid, wg, 0, (hipStream_t)stream, (uint64_t *)d_out, ow, (const uint64_t *)in0, w0,
                            (const uint64_t *)in1, w1, (uint32_t)batch, cstm);
+    return finish_launch();
+}
+
+int ntt_xof_ragged(uint8_t *d_out, size_t outlen, const uint8_t *d_msg, size_t msg_bytes, const uint64_t *d_off, size_t batch,
+                   int algo, int cstm, void *stream)
+{
+    if ((algo != NTT_XOF_SHAKE128 && algo != NTT_XOF_SHAKE256) || cstm < -1 || cstm > 65535) return NTT_ERR_PARAM;
+    if ((outlen & 7u) || outlen < 8 || outlen > NTT_XOF_OUT_MAX || (msg_bytes & 7u)) return NTT_ERR_PARAM;
+    if (batch == 0) return NTT_OK;
+    // an empty buffer is never read: its pointer takes part in no check
+    const uint8_t *msg = msg_bytes ? d_msg : nullptr;
+    if (!d_out || !d_off || (msg_bytes && !msg)) return NTT_ERR_NULL;
+    if ((((uintptr_t)d_out) | ((uintptr_t)d_off) | ((uintptr_t)msg)) & 7u) return NTT_ERR_ALIGN;
+    if (batch > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
+    const size_t obytes = batch * outlen;
+    if ((msg_bytes && ranges_overlap(d_out, obytes, msg, msg_bytes)) || ranges_overlap(d_out, obytes, d_off, 8 * (batch + 1)))
+        return NTT_ERR_ALIAS;
+    int rc;
+    DevInfo *d = nullptr;
+    if ((rc = device_ready(&d)) != NTT_OK) return rc;
+    const dim3 grid((uint32_t)ceil_div(batch, (size_t)XOF_WG)), wg(XOF_WG);
+    const uint32_t ow = (uint32_t)(outlen / 8);
+    if (algo == NTT_XOF_SHAKE128)
+        hipLaunchKernelGGL(k_xof_ragged<XOF_RATE128>, grid, wg, 0, (hipStream_t)stream, (uint64_t *)d_out, ow, (const uint64_t *)msg,
+                           (uint64_t)msg_bytes, d_off, (uint32_t)batch, cstm);
+    else
+        hipLaunchKernelGGL(k_xof_ragged<XOF_RATE256>, grid, wg, 0, (hipStream_t)stream, (uint64_t *)d_out, ow, (const uint64_t *)msg,
+                           (uint64_t)msg_bytes, d_off, (uint32_t)batch, cstm);
     return finish_launch();
 }
 

@@ -97,6 +97,7 @@ def lib():
         L.poly_mul_ntt_kl_round_keyed.argtypes = [_vp, _vp, ctypes.POINTER(_vp), _vp, _vp, _sz, _vp, _sz, ctypes.c_int,
                                                   ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
         L.ntt_xof.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, _vp]
+        L.ntt_xof_ragged.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_challenge.argtypes = [_vp, _vp, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_sample_y.argtypes = [_vp, _vp, _sz, _vp, ctypes.c_uint32, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_gen_a.argtypes = [_vp, _sz, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
@@ -699,6 +700,65 @@ def xof(out, in0, in1=None, algo="shake256", cstm=None, stream=None):
     fn = lib().ntt_xof
     _run("ntt_xof", tensors, stream, lambda s: fn(out.data_ptr(), outlen, p0, len0, p1, len1, nb, a, c, s))
     return out
+
+
+def xof_ragged(out, msg, off, algo="shake256", cstm=None, stream=None):
+    """out[b] = XOF(msg[off[b] : off[b + 1]]) for every b, one launch: xof's
+    hash over messages of any byte length, back to back in msg (qTESLA's
+    G(m) from the messages as they arrive).
+
+    out is [batch, outlen] int8/uint8 (outlen a multiple of 8 within 8 .. 512);
+    msg a contiguous 1-D int8/uint8 device tensor whose numel is a multiple of
+    8 (the caller pads the buffer: the kernel reads aligned 8-byte words); off a
+    contiguous int64 device tensor of batch + 1 byte offsets, its bits taken as
+    uint64.  Offsets are clamped to the buffer and to each other as
+    ntt_xof_ragged defines (qtesla_ntt.h); a well-formed table is non-decreasing
+    and ends at or below msg.numel().  Dtypes and shapes are checked before the
+    devices.  Returns out."""
+    torch = _torch()
+    for name, t in (("out", out), ("msg", msg)):
+        if t.dtype not in (torch.int8, torch.uint8):
+            raise TypeError(f"{name}: expected int8/uint8 storage, got {t.dtype}")
+    if off.dtype != torch.int64:
+        raise TypeError(f"off: expected int64 storage (the offsets' uint64 bits), got {off.dtype}")
+    if out.dim() != 2:
+        raise ValueError(f"out: shape {tuple(out.shape)}, expected [batch, bytes]")
+    nb, outlen = out.shape
+    if outlen % 8 or not 8 <= outlen <= XOF_OUT_MAX:
+        raise ValueError(f"out: {outlen} bytes per message, expected a multiple of 8 within 8 .. {XOF_OUT_MAX}")
+    if msg.dim() != 1:
+        raise ValueError(f"msg: shape {tuple(msg.shape)}, expected one dimension (all messages back to back)")
+    msg_bytes = msg.numel()
+    if msg_bytes % 8:
+        raise ValueError(f"msg: {msg_bytes} bytes, expected a multiple of 8: pad the buffer to whole 8-byte words "
+                         "(the pad bytes belong to no message)")
+    if off.dim() != 1 or off.numel() != nb + 1:
+        raise ValueError(f"off: shape {tuple(off.shape)}, expected [{nb + 1}] (batch + 1 offsets)")
+    for name, t in (("out", out), ("msg", msg), ("off", off)):
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: tensor must be contiguous")
+    if isinstance(algo, str) and algo not in XOF_ALGOS:
+        raise ValueError(f"algo {algo!r}, expected one of {sorted(XOF_ALGOS)}")
+    a = XOF_ALGOS[algo] if isinstance(algo, str) else int(algo)
+    c = -1 if cstm is None else int(cstm)
+    if cstm is not None and not 0 <= c <= 0xFFFF:
+        raise ValueError(f"cstm = {cstm}, expected None or 0 .. 65535")
+    pm = msg.data_ptr() if msg_bytes else None
+    fn = lib().ntt_xof_ragged
+    _run("ntt_xof_ragged", (out, msg, off), stream, lambda s: fn(out.data_ptr(), outlen, pm, msg_bytes, off.data_ptr(), nb, a, c, s))
+    return out
+
+
+def ragged_pack(messages, device):
+    """A list of bytes to xof_ragged's (msg, off) on `device`: the messages back
+    to back, zero-padded to a multiple of 8 bytes, and their batch + 1 offsets.
+    A host helper for tests and small callers (one copy per call)."""
+    torch = _torch()
+    off = np.zeros(len(messages) + 1, dtype=np.int64)
+    np.cumsum(np.array([len(m) for m in messages], dtype=np.int64), out=off[1:])
+    data = b"".join(messages)
+    buf = np.frombuffer(data + bytes(-len(data) % 8), dtype=np.uint8).copy()
+    return torch.from_numpy(buf).to(device), torch.from_numpy(off).to(device)
 
 
 def poly_challenge(pos, val, seed, param_set, stream=None):
