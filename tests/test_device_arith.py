@@ -6,79 +6,22 @@ twiddles), the signed Shoup product and BaseMul's zeta-split residue
 products.  Checks congruence mod q and the output ranges the kernels rely on,
 over edge values and random samples, for every prime.  The GPU parity tests
 check the kernels themselves; this pins the bounds the static_asserts and
-comments state."""
+comments state.
+
+The model lives in tests/arith_model.py, which also restates every other
+inlined primitive (numpy, word-exact), builds the operand grid and states each
+primitive's claim; tests/test_gpu_device_arith.py runs the device functions
+over that grid and compares them with the claims and with the model word for
+word.  The second half of this module keeps the CPU side of that honest: the
+model satisfies every claim over the whole grid, the library's constant
+builders equal their definitions, and the grid rejects seven deliberate errors."""
 import random
 
+import numpy as np
 import pytest
 
-PRIMES = {"ref": 8404993, "p-I": 343576577, "p-III": 856145921}
-M32 = (1 << 32) - 1
-M64 = (1 << 64) - 1
-
-
-def s32(x):
-    x &= M32
-    return x - (1 << 32) if x >> 31 else x
-
-
-def shoup(w, q):
-    return (w << 32) // q
-
-
-def centred(w, q):
-    """csigned_tw (pset.hpp): ws in (-q/2, q/2], wps = floor(ws 2^32 / q)."""
-    ws = w if w <= q // 2 else w - q
-    return ws, (ws << 32) // q   # Python // floors, as the device constant does
-
-
-def madlo32(a, b, c):
-    return (a * b + c) & M32
-
-
-def umulhi(a, b):
-    return ((a & M32) * (b & M32)) >> 32
-
-
-def sq_quot(y, wps):
-    """e = floor((d * wps - 2^31) / 2^32), d and wps signed (v_mad_i64_i32)."""
-    return ((s32(y) * s32(wps) - (1 << 31)) >> 32) & M32
-
-
-def ct_bfly_t(x, y, w, q, red, xs, ys, yos):
-    """ntt_device.hpp ct_bfly_t with the twiddle w in [0, q): returns (x', y')
-    as 32-bit words.  Unsigned y: (2^32 - w, w'); signed y: (-ws, ws')."""
-    if not red:
-        a = x
-    elif xs:
-        a = min(x, (x + 2 * q) & M32)
-    else:
-        a = min(x, (x - 2 * q) & M32)
-    if ys:
-        ws, wps = centred(w, q)
-        qe = sq_quot(y, wps & M32)
-        tn = madlo32(qe, q, (y * ((-ws) & M32)) & M32)
-    else:
-        qe = umulhi(y, shoup(w, q))
-        tn = madlo32(qe, q, (y * ((-w) & M32)) & M32)
-    xo = (a - tn) & M32
-    yo = (a + tn) & M32 if yos else (a + tn + 2 * q) & M32
-    return xo, yo
-
-
-def value(word, s):
-    """the integer a word stands for: S form is signed"""
-    return s32(word) if s else word
-
-
-def samples(q, s, rng, k=400):
-    """edge and random words of a U ([0, 4q)) or S ((-2q, 2q)) operand"""
-    if s:
-        edge = [0, 1, -1, q - 1, -(q - 1), q, -q, 2 * q - 1, -(2 * q - 1)]
-        rnd = [rng.randrange(-2 * q + 1, 2 * q) for _ in range(k)]
-    else:
-        edge = [0, 1, q - 1, q, 2 * q - 1, 2 * q, 4 * q - 1]
-        rnd = [rng.randrange(0, 4 * q) for _ in range(k)]
-    return [v & M32 for v in edge + rnd]
+import arith_model as AM
+from arith_model import M32, M64, PRIMES, centred, ct_bfly_t, fwd_signed_table, madlo32, redc, s32, samples, shoup, sq_quot, umulhi, value
 
 
 @pytest.mark.parametrize("name", list(PRIMES))
@@ -130,16 +73,6 @@ def test_signed_shoup_range(name):
         assert (t - d * w) % q == 0
 
 
-def fwd_signed_table(q, psi, logn):
-    """FwdSignedTw<P>: (-ws mod 2^32, wps) of psi^brv(k), k < 32"""
-    out = []
-    for k in range(32):
-        e = int(format(k, f"0{logn}b")[::-1], 2)
-        ws, wps = centred(pow(psi, e, q), q)
-        out.append(((-ws) & M32, wps & M32))
-    return out
-
-
 def test_fwd_signed_table_is_the_fwd_table_centred(ntt):
     """the compile-time signed pass-1 twiddles name the same psi^brv(k) as the
     library's tables (ntt_get_tables Phi[i] = psi^i)"""
@@ -153,11 +86,6 @@ def test_fwd_signed_table_is_the_fwd_table_centred(ntt):
             w = int(phi[int(format(k, f"0{logn}b")[::-1], 2)])
             ws, wps = centred(w, q)
             assert tab[k] == ((-ws) & M32, wps & M32)
-
-
-def redc(c, q, qneg):
-    m = (c * qneg) & M32
-    return ((m * q + c) >> 32)
 
 
 @pytest.mark.parametrize("name", list(PRIMES))
@@ -239,3 +167,128 @@ def test_half_canonical_residue_product_and_wide_first_stage(name):
         xo = min(sm, (sm - 2 * q) & M32, (sm - 4 * q) & M32)
         assert xo == (x + y) % (2 * q)
         assert abs(x - y) < 2 ** 31
+
+
+# --------------------------------------------------------------------------
+# arith_model: the vector model, the operand grid and the claims that
+# tests/test_gpu_device_arith.py runs against the device functions themselves
+# --------------------------------------------------------------------------
+CASE_IDS = [f"{p}-v{v}" for p, v in AM.CASES]
+
+
+@pytest.fixture(scope="module")
+def twiddles(ntt):
+    """the grid's twiddle sets, from the library's own Phi / invPhi tables,
+    which are what arith_model.model_tables restates"""
+    out = {}
+    for name, q in PRIMES.items():
+        t = ntt.tables(name)
+        phi, inv = AM.model_tables(q)
+        assert np.array_equal(t["Phi"], phi) and np.array_equal(t["invPhi"], inv)
+        out[name] = AM.twiddle_set(q, t["Phi"], t["invPhi"])
+    return out
+
+
+@pytest.mark.parametrize("name", list(PRIMES))
+def test_vector_model_is_the_scalar_model(name):
+    """the numpy model (what the GPU outputs are compared with word for word)
+    and the scalar helpers above agree on every typed butterfly form"""
+    q = PRIMES[name]
+    rng = random.Random(17)
+    for form in AM.CT_FORMS:
+        red, xs, ys, yos = form
+        xw = samples(q, xs, rng, 60) if red else [rng.randrange(2 * q) for _ in range(60)]
+        yw = samples(q, ys, rng, len(xw) - (9 if ys else 7))
+        ws = [rng.randrange(q) for _ in xw]
+        wn, wp = AM.tw_pair(ws, q, "fwd_signed" if ys else "fwd")
+        got = AM.v_ct_bfly_t(AM.words(xw), AM.words(yw), wn, wp, q, *form)
+        want = [ct_bfly_t(x, y, w, q, *form) for x, y, w in zip(xw, yw, ws)]
+        assert [(int(a), int(b)) for a, b in zip(*got)] == want
+
+
+@pytest.mark.parametrize("name", list(PRIMES))
+@pytest.mark.parametrize("prim,variant", AM.CASES, ids=CASE_IDS)
+def test_model_stays_inside_every_claim(twiddles, name, prim, variant):
+    """check() accepts the model's outputs over the whole grid: the reference
+    of the GPU test satisfies every claim that test makes"""
+    q = PRIMES[name]
+    inputs = AM.grid(prim, q, variant, twiddles[name])
+    assert len(inputs) == AM.PRIMS[prim][1] and len({len(c) for c in inputs}) == 1
+    outputs = AM.model(prim, q, inputs, variant)
+    assert len(outputs) == AM.PRIMS[prim][2]
+    AM.check(prim, q, inputs, outputs, variant)
+
+
+@pytest.mark.parametrize("name", list(PRIMES))
+@pytest.mark.parametrize("mutant", list(AM.MUTANTS))
+def test_grid_rejects_mutant(twiddles, name, mutant):
+    """the grid has teeth: each deliberate error of the model breaks a claim
+    on at least one tuple of the same grid, for every prime"""
+    q = PRIMES[name]
+    for prim, variant in AM.MUTANTS[mutant]:
+        inputs = AM.grid(prim, q, variant, twiddles[name])
+        outputs = AM.model(prim, q, inputs, variant, mutant=mutant)
+        nbad = int(AM.violations(prim, q, inputs, outputs, variant).sum())
+        assert nbad > 0, f"{mutant} passes {prim} v{variant}"
+        with pytest.raises(AssertionError, match="first at"):
+            AM.check(prim, q, inputs, outputs, variant)
+
+
+@pytest.fixture(scope="module")
+def probe_host(ntt):
+    """the probe library's host entry points; they need no device"""
+    import arith_probe
+    try:
+        return arith_probe, arith_probe.load(ntt)
+    except OSError as e:
+        pytest.skip(f"{arith_probe.path(ntt)} does not load without a device: {e}")
+
+
+@pytest.mark.parametrize("name", list(PRIMES))
+def test_constant_builders(probe_host, name):
+    """cshoup, csigned_tw, cqinv_neg and the per-set constants of pset.hpp, as
+    the library's own constexpr functions compute them, equal the definitions"""
+    AP, L = probe_host
+    q, n, psi = AM.SETS[name]
+    C = AP.consts(L, name)
+    assert (C["Q"], C["N"], C["PSI"], C["MUL_LOGR"]) == (q, n, psi, AM.MUL_LOGR)
+    assert C["QNEG"] == (-pow(q, -1, 1 << 32)) & M32 == L.arith_probe_cqinv_neg(q)
+    assert C["R"] == (1 << 32) % q
+    assert C["NINV"] == pow(n, -1, q) and C["C1"] == pow(n, -1, q) * pow(psi, -(n // 2), q) % q
+    assert C["NINV_R"] == C["NINV"] * C["R"] % q and C["C1_R"] == C["C1"] * C["R"] % q
+    assert C["NINV_R_SHORT"] == pow(n >> AM.MUL_LOGR, -1, q) * C["R"] % q   # (n / 2^LOGR)^-1 2^32
+    assert C["C1_R_SHORT"] == pow(n >> AM.MUL_LOGR, -1, q) * pow(psi, -(n // 2), q) * C["R"] % q
+    mine = AM.consts(q)
+    for k in AP.CONST_NAMES:
+        if k != "MUL_LOGR":
+            assert C[k] == int(mine[k]), k
+    tw = AM.twiddle_set(q, *AM.model_tables(q))
+    ws = [0] + [int(w) for w in tw["fixed"]] + [int(w) for w in tw["table"][:: max(1, len(tw["table"]) // 512)]]
+    ws += [q // 2 - 1, q // 2, q // 2 + 1, q // 2 + 2]
+    for w in ws:
+        assert L.arith_probe_cshoup(w, q) == (w << 32) // q
+        cs, cp = centred(w, q)
+        assert -q // 2 < cs <= q // 2 and (cs - w) % q == 0
+        assert AP.csigned_tw(L, w, q) == (cs & M32, cp & M32)
+    a, b = AM.tw_pair(ws, q, "signed")
+    assert [(int(x), int(y)) for x, y in zip(a, b)] == [AP.csigned_tw(L, w, q) for w in ws]
+
+
+@pytest.mark.parametrize("name", list(PRIMES))
+def test_aimed_tuples_reach_the_ends(twiddles, name):
+    """the grid's aimed operands do what their construction says: the unsigned
+    lazy product sits one q above its residue and comes within q^2 / 2^32 of
+    2q; the signed one comes that near to both ends of (0, 2q)"""
+    q = PRIMES[name]
+    ws = AM.aim_twiddles(q, twiddles[name])
+    slack = (q * q >> 32) + 4
+    a, w = (np.array(c, dtype=np.int64) for c in zip(*AM.aimed_unsigned(q, ws, 1 << 32)))
+    out = AM.model("shoup_mul", q, [AM.words(a), *AM.tw_pair(w, q, "shoup")])[0]
+    assert [int(o) for o in out] == [int(x) * int(y) % q + q for x, y in zip(a, w)]
+    assert 2 * q - slack <= int(out.max()) < 2 * q
+    d, w = (np.array(c, dtype=np.int64) for c in zip(*AM.aimed_signed(q, ws, 1 << 31)))
+    assert np.abs(d).max() < 1 << 31
+    out = AM.model("sshoup_mul", q, [AM.words(d), *AM.tw_pair(w, q, "signed")])[0]
+    assert 0 < int(out.min()) <= slack and 2 * q - slack <= int(out.max()) < 2 * q
+    d, w = (np.array(c, dtype=np.int64) for c in zip(*AM.aimed_signed(q, ws, 2 * q)))
+    assert np.abs(d).max() < 2 * q   # what gs_bfly and an S-form y can hold
