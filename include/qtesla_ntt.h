@@ -303,13 +303,34 @@ int poly_mul_ntt_kl_round_keyed(uint8_t *d_hi, uint32_t *d_norms, const uint32_t
  *   NTT_ERR_ALIGN  any of the three pointers not 8-byte aligned
  *   NTT_ERR_SIZE   batch > 2^31 - 1
  *   NTT_ERR_ALIAS  d_out overlaps an input (the inputs may overlap each other)
- * One message per lane: the throughput comes from the batch, and a batch of 1
- * costs the same serial chain of permutations as a batch of thousands. */
+ * Two kernel families give the same bytes: one message per lane, whose
+ * throughput comes from the batch, and two messages per wave (the sponge's
+ * state spread over the lanes), whose chain of permutations is shorter.
+ * ntt_xof runs the second for batch <= ntt_xof_small_batch_max(algo, 0, .) and
+ * the first above; ntt_xof_path takes the choice as an argument.
+ *
+ * ntt_xof_path is ntt_xof with the kernel family named: NTT_XOF_PATH_AUTO is
+ * ntt_xof itself, NTT_XOF_PATH_LANE and NTT_XOF_PATH_WAVE run one family at
+ * every batch.  All three give identical bytes for every legal input.  A path
+ * outside 0 .. 2 is NTT_ERR_PARAM, with the first check; every other check,
+ * its order and its code are ntt_xof's.
+ * ntt_xof_small_batch_max: the largest batch at which NTT_XOF_PATH_AUTO runs
+ * the wave kernels (0: never), for ntt_xof (ragged = 0) or ntt_xof_ragged
+ * (ragged = 1).  NTT_ERR_PARAM for an unknown algo or a ragged outside 0 / 1,
+ * then NTT_ERR_NULL for a NULL max_batch. */
 #define NTT_XOF_SHAKE128 0   /* rate 168 */
 #define NTT_XOF_SHAKE256 1   /* rate 136 */
 #define NTT_XOF_OUT_MAX 512
+#define NTT_XOF_PATH_AUTO 0   /* what ntt_xof / ntt_xof_ragged do */
+#define NTT_XOF_PATH_LANE 1   /* one message per lane (k_xof, k_xof_ragged) */
+#define NTT_XOF_PATH_WAVE 2   /* two messages per wave */
 int ntt_xof(uint8_t *d_out, size_t outlen, const uint8_t *d_in0, size_t len0,
             const uint8_t *d_in1, size_t len1, size_t batch, int algo, int cstm, void *stream);
+int ntt_xof_path(uint8_t *d_out, size_t outlen, const uint8_t *d_in0, size_t len0,
+                 const uint8_t *d_in1, size_t len1, size_t batch, int algo, int cstm, int path,
+                 void *stream);
+/* largest batch at which PATH_AUTO runs the wave kernels (0 = never) */
+int ntt_xof_small_batch_max(int algo, int ragged, size_t *max_batch);
 
 /* ntt_xof's hash over messages of any byte length, each its own, one launch --
  * qTESLA's G(m), the 64-byte digest of every message of a batch, from the
@@ -352,13 +373,21 @@ int ntt_xof(uint8_t *d_out, size_t outlen, const uint8_t *d_in0, size_t len0,
  *   NTT_ERR_ALIAS  d_out's batch * outlen bytes overlap d_msg's msg_bytes or
  *                  d_off's 8 (batch + 1) bytes (the two inputs may overlap each
  *                  other)
- * One message per lane, one launch for every batch size.  A wave of 64
+ * One launch for every batch size.  With one message per lane a wave of 64
  * consecutive messages costs its longest message's serial chain of
- * permutations: a caller with very uneven lengths should sort or bucket the
- * messages by length.  There is no cooperative path for one huge message, and
- * a small batch is as slow as ntt_xof's: the throughput comes from the batch. */
+ * permutations, and with two messages per wave the pair costs the longer
+ * one's: a caller with very uneven lengths should sort or bucket the messages
+ * by length.  There is no cooperative path for one huge message.
+ * ntt_xof_ragged runs two messages per wave for batch <=
+ * ntt_xof_small_batch_max(algo, 1, .) and one message per lane above;
+ * ntt_xof_ragged_path takes the choice as an argument, as ntt_xof_path does:
+ * identical bytes on every path, a path outside 0 .. 2 is NTT_ERR_PARAM with
+ * the first check, everything else is ntt_xof_ragged's. */
 int ntt_xof_ragged(uint8_t *d_out, size_t outlen, const uint8_t *d_msg, size_t msg_bytes,
                    const uint64_t *d_off, size_t batch, int algo, int cstm, void *stream);
+int ntt_xof_ragged_path(uint8_t *d_out, size_t outlen, const uint8_t *d_msg, size_t msg_bytes,
+                        const uint64_t *d_off, size_t batch, int algo, int cstm, int path,
+                        void *stream);
 
 /* qTESLA's Enc(c'): a seed to the h positions and signs of the challenge,
  * exactly the lists poly_scatter takes.

@@ -29,6 +29,7 @@
 #include "ntt_unpack_ntt.hpp"
 #include "ntt_xof.hpp"
 #include "ntt_xof_ragged.hpp"
+#include "ntt_xof_wave.hpp"
 #include "ntt_internal.h"
 #include "params.hpp"
 #include "pset.hpp"
@@ -807,9 +808,27 @@ int poly_mul_ntt_kl_round_keyed(uint8_t *d_hi, uint32_t *d_norms, const uint32_t
     return mul_kl_round_common(d_hi, d_norms, RowOps{d_y, l, d_ahat, d_add, d_key, nkeys}, true, batch, k, d, ps, stream);
 }
 
-int ntt_xof(uint8_t *d_out, size_t outlen, const uint8_t *d_in0, size_t len0, const uint8_t *d_in1, size_t len1,
-            size_t batch, int algo, int cstm, void *stream)
+// Largest batch at which NTT_XOF_PATH_AUTO runs the wave kernels (two messages
+// per wave, ntt_xof_wave.hpp), per [ragged][algo]: measured, DESIGN.md section 5q
+static constexpr size_t kXofWaveMax[2][2] = {{8192, 8192}, {8192, 8192}};
+
+static bool xof_takes_wave(int path, int ragged, int algo, size_t batch)
 {
+    return path == NTT_XOF_PATH_WAVE || (path == NTT_XOF_PATH_AUTO && batch <= kXofWaveMax[ragged][algo]);
+}
+
+// one workgroup per XOF_WAVE_WG / 64 waves, one wave per two messages, in rows of XOF_WAVE_GRID_X workgroups (a grid
+// dimension holds fewer than 2^32 threads, batch = 2^31 - 1 needs 2^36)
+static dim3 xof_wave_grid(size_t batch)
+{
+    const size_t wgs = ceil_div(ceil_div(batch, (size_t)2) * 64, (size_t)XOF_WAVE_WG);
+    return dim3((uint32_t)(wgs < XOF_WAVE_GRID_X ? wgs : XOF_WAVE_GRID_X), (uint32_t)ceil_div(wgs, (size_t)XOF_WAVE_GRID_X));
+}
+
+int ntt_xof_path(uint8_t *d_out, size_t outlen, const uint8_t *d_in0, size_t len0, const uint8_t *d_in1, size_t len1,
+                 size_t batch, int algo, int cstm, int path, void *stream)
+{
+    if (path < NTT_XOF_PATH_AUTO || path > NTT_XOF_PATH_WAVE) return NTT_ERR_PARAM;
     if ((algo != NTT_XOF_SHAKE128 && algo != NTT_XOF_SHAKE256) || cstm < -1 || cstm > 65535) return NTT_ERR_PARAM;
     if ((len0 & 7u) || (len1 & 7u) || len0 >= ((size_t)1 << 32) || len1 >= ((size_t)1 << 32) ||
         len0 + len1 >= ((size_t)1 << 32))
@@ -827,20 +846,27 @@ int ntt_xof(uint8_t *d_out, size_t outlen, const uint8_t *d_in0, size_t len0, co
     int rc;
     DevInfo *d = nullptr;
     if ((rc = device_ready(&d)) != NTT_OK) return rc;
-    const dim3 grid((uint32_t)ceil_div(batch, (size_t)XOF_WG)), wg(XOF_WG);
+    const bool wave = xof_takes_wave(path, 0, algo, batch);
+    const dim3 grid = wave ? xof_wave_grid(batch) : dim3((uint32_t)ceil_div(batch, (size_t)XOF_WG));
+    const dim3 wg(wave ? XOF_WAVE_WG : XOF_WG);
     const uint32_t ow = (uint32_t)(outlen / 8), w0 = (uint32_t)(len0 / 8), w1 = (uint32_t)(len1 / 8);
-    if (algo == NTT_XOF_SHAKE128)
-        hipLaunchKernelGGL(k_xof<XOF_RATE128>, grid, wg, 0, (hipStream_t)stream, (uint64_t *)d_out, ow, (const uint64_t *)in0, w0,
-                           (const uint64_t *)in1, w1, (uint32_t)batch, cstm);
-    else
-        hipLaunchKernelGGL(k_xof<XOF_RATE256>, grid, wg, 0, (hipStream_t)stream, (uint64_t *)d_out, ow, (const uint64_t *)in0, w0,
-                           (const uint64_t *)in1, w1, (uint32_t)batch, cstm);
+    auto *const k = algo == NTT_XOF_SHAKE128 ? (wave ? k_xof_wave<XOF_RATE128> : k_xof<XOF_RATE128>)
+                                             : (wave ? k_xof_wave<XOF_RATE256> : k_xof<XOF_RATE256>);
+    hipLaunchKernelGGL(k, grid, wg, 0, (hipStream_t)stream, (uint64_t *)d_out, ow, (const uint64_t *)in0, w0,
+                       (const uint64_t *)in1, w1, (uint32_t)batch, cstm);
     return finish_launch();
 }
 
-int ntt_xof_ragged(uint8_t *d_out, size_t outlen, const uint8_t *d_msg, size_t msg_bytes, const uint64_t *d_off, size_t batch,
-                   int algo, int cstm, void *stream)
+int ntt_xof(uint8_t *d_out, size_t outlen, const uint8_t *d_in0, size_t len0, const uint8_t *d_in1, size_t len1,
+            size_t batch, int algo, int cstm, void *stream)
 {
+    return ntt_xof_path(d_out, outlen, d_in0, len0, d_in1, len1, batch, algo, cstm, NTT_XOF_PATH_AUTO, stream);
+}
+
+int ntt_xof_ragged_path(uint8_t *d_out, size_t outlen, const uint8_t *d_msg, size_t msg_bytes, const uint64_t *d_off,
+                        size_t batch, int algo, int cstm, int path, void *stream)
+{
+    if (path < NTT_XOF_PATH_AUTO || path > NTT_XOF_PATH_WAVE) return NTT_ERR_PARAM;
     if ((algo != NTT_XOF_SHAKE128 && algo != NTT_XOF_SHAKE256) || cstm < -1 || cstm > 65535) return NTT_ERR_PARAM;
     if ((outlen & 7u) || outlen < 8 || outlen > NTT_XOF_OUT_MAX || (msg_bytes & 7u)) return NTT_ERR_PARAM;
     if (batch == 0) return NTT_OK;
@@ -855,15 +881,29 @@ int ntt_xof_ragged(uint8_t *d_out, size_t outlen, const uint8_t *d_msg, size_t m
     int rc;
     DevInfo *d = nullptr;
     if ((rc = device_ready(&d)) != NTT_OK) return rc;
-    const dim3 grid((uint32_t)ceil_div(batch, (size_t)XOF_WG)), wg(XOF_WG);
+    const bool wave = xof_takes_wave(path, 1, algo, batch);
+    const dim3 grid = wave ? xof_wave_grid(batch) : dim3((uint32_t)ceil_div(batch, (size_t)XOF_WG));
+    const dim3 wg(wave ? XOF_WAVE_WG : XOF_WG);
     const uint32_t ow = (uint32_t)(outlen / 8);
-    if (algo == NTT_XOF_SHAKE128)
-        hipLaunchKernelGGL(k_xof_ragged<XOF_RATE128>, grid, wg, 0, (hipStream_t)stream, (uint64_t *)d_out, ow, (const uint64_t *)msg,
-                           (uint64_t)msg_bytes, d_off, (uint32_t)batch, cstm);
-    else
-        hipLaunchKernelGGL(k_xof_ragged<XOF_RATE256>, grid, wg, 0, (hipStream_t)stream, (uint64_t *)d_out, ow, (const uint64_t *)msg,
-                           (uint64_t)msg_bytes, d_off, (uint32_t)batch, cstm);
+    auto *const k = algo == NTT_XOF_SHAKE128 ? (wave ? k_xof_ragged_wave<XOF_RATE128> : k_xof_ragged<XOF_RATE128>)
+                                             : (wave ? k_xof_ragged_wave<XOF_RATE256> : k_xof_ragged<XOF_RATE256>);
+    hipLaunchKernelGGL(k, grid, wg, 0, (hipStream_t)stream, (uint64_t *)d_out, ow, (const uint64_t *)msg, (uint64_t)msg_bytes,
+                       d_off, (uint32_t)batch, cstm);
     return finish_launch();
+}
+
+int ntt_xof_ragged(uint8_t *d_out, size_t outlen, const uint8_t *d_msg, size_t msg_bytes, const uint64_t *d_off, size_t batch,
+                   int algo, int cstm, void *stream)
+{
+    return ntt_xof_ragged_path(d_out, outlen, d_msg, msg_bytes, d_off, batch, algo, cstm, NTT_XOF_PATH_AUTO, stream);
+}
+
+int ntt_xof_small_batch_max(int algo, int ragged, size_t *max_batch)
+{
+    if ((algo != NTT_XOF_SHAKE128 && algo != NTT_XOF_SHAKE256) || ragged < 0 || ragged > 1) return NTT_ERR_PARAM;
+    if (!max_batch) return NTT_ERR_NULL;
+    *max_batch = kXofWaveMax[ragged][algo];
+    return NTT_OK;
 }
 
 int poly_challenge(uint32_t *d_pos, uint32_t *d_val, const uint8_t *d_seed, size_t seedlen, size_t batch, int h, int ps,

@@ -98,6 +98,9 @@ def lib():
                                                   ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
         L.ntt_xof.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.ntt_xof_ragged.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
+        L.ntt_xof_path.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
+        L.ntt_xof_ragged_path.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
+        L.ntt_xof_small_batch_max.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(_sz)]
         L.poly_challenge.argtypes = [_vp, _vp, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_sample_y.argtypes = [_vp, _vp, _sz, _vp, ctypes.c_uint32, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_gen_a.argtypes = [_vp, _sz, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
@@ -648,6 +651,8 @@ def poly_mul_ntt_kl_round_keyed(ys, ahat, keys, param_set, d: int, hi=None, norm
 
 XOF_ALGOS = {"shake128": 0, "shake256": 1}   # NTT_XOF_SHAKE128, NTT_XOF_SHAKE256
 XOF_OUT_MAX = 512          # NTT_XOF_OUT_MAX
+XOF_PATHS = {"auto": 0, "lane": 1, "wave": 2}   # NTT_XOF_PATH_AUTO, NTT_XOF_PATH_LANE, NTT_XOF_PATH_WAVE
+XOF_PATH_AUTO, XOF_PATH_LANE, XOF_PATH_WAVE = 0, 1, 2
 CHALLENGE_H_MAX = 128      # NTT_CHALLENGE_H_MAX
 SAMPLE_Y_REFILLS_MAX = 255   # NTT_SAMPLE_Y_REFILLS_MAX
 GEN_A_BLOCKS_MAX = 256       # NTT_GEN_A_BLOCKS_MAX
@@ -668,7 +673,24 @@ def _byte_rows(name: str, t, batch: int) -> int:
     return row
 
 
-def xof(out, in0, in1=None, algo="shake256", cstm=None, stream=None):
+def _xof_path(path) -> int:
+    if path not in XOF_PATHS:
+        raise ValueError(f"path {path!r}, expected one of {sorted(XOF_PATHS)}")
+    return XOF_PATHS[path]
+
+
+def xof_small_batch_max(algo="shake256", ragged: bool = False) -> int:
+    """Largest batch at which xof (ragged False) or xof_ragged (ragged True)
+    with path="auto" runs the wave kernels, two messages per wave (0: never)."""
+    if isinstance(algo, str) and algo not in XOF_ALGOS:
+        raise ValueError(f"algo {algo!r}, expected one of {sorted(XOF_ALGOS)}")
+    a = XOF_ALGOS[algo] if isinstance(algo, str) else int(algo)
+    v = _sz()
+    _check(lib().ntt_xof_small_batch_max(a, int(bool(ragged)), ctypes.byref(v)), "ntt_xof_small_batch_max")
+    return v.value
+
+
+def xof(out, in0, in1=None, algo="shake256", cstm=None, stream=None, path="auto"):
     """out[b] = XOF(in0[b] || in1[b]) for every b, one launch: SHAKE128 /
     SHAKE256 (cstm None) or qTESLA's cshake128_simple / cshake256_simple with
     the 16-bit customization cstm (qTESLA's H, G and the expansions).
@@ -677,7 +699,10 @@ def xof(out, in0, in1=None, algo="shake256", cstm=None, stream=None):
     the batch ([batch, k, n] hi bytes are taken as they are); in1 may be None
     (one segment).  Bytes per message: multiples of 8, out's within
     8 .. 512.  The two segments are read where they lie; out overlaps
-    neither.  Returns out."""
+    neither.  path: "auto" (two messages per wave up to xof_small_batch_max,
+    one message per lane above), "lane" or "wave" -- the same bytes on each.
+    Returns out."""
+    pth = _xof_path(path)
     if out.dim() < 2:
         raise ValueError(f"out: shape {tuple(out.shape)}, expected [batch, bytes]")
     nb = out.shape[0]
@@ -697,12 +722,12 @@ def xof(out, in0, in1=None, algo="shake256", cstm=None, stream=None):
     p0 = in0.data_ptr() if len0 else None
     p1 = in1.data_ptr() if len1 else None
     tensors = (out, in0) if in1 is None else (out, in0, in1)
-    fn = lib().ntt_xof
-    _run("ntt_xof", tensors, stream, lambda s: fn(out.data_ptr(), outlen, p0, len0, p1, len1, nb, a, c, s))
+    fn = lib().ntt_xof_path
+    _run("ntt_xof", tensors, stream, lambda s: fn(out.data_ptr(), outlen, p0, len0, p1, len1, nb, a, c, pth, s))
     return out
 
 
-def xof_ragged(out, msg, off, algo="shake256", cstm=None, stream=None):
+def xof_ragged(out, msg, off, algo="shake256", cstm=None, stream=None, path="auto"):
     """out[b] = XOF(msg[off[b] : off[b + 1]]) for every b, one launch: xof's
     hash over messages of any byte length, back to back in msg (qTESLA's
     G(m) from the messages as they arrive).
@@ -713,8 +738,9 @@ def xof_ragged(out, msg, off, algo="shake256", cstm=None, stream=None):
     contiguous int64 device tensor of batch + 1 byte offsets, its bits taken as
     uint64.  Offsets are clamped to the buffer and to each other as
     ntt_xof_ragged defines (qtesla_ntt.h); a well-formed table is non-decreasing
-    and ends at or below msg.numel().  Dtypes and shapes are checked before the
-    devices.  Returns out."""
+    and ends at or below msg.numel().  path as xof's, with
+    xof_small_batch_max(algo, ragged=True).  Dtypes and shapes are checked
+    before the devices.  Returns out."""
     torch = _torch()
     for name, t in (("out", out), ("msg", msg)):
         if t.dtype not in (torch.int8, torch.uint8):
@@ -744,8 +770,10 @@ def xof_ragged(out, msg, off, algo="shake256", cstm=None, stream=None):
     if cstm is not None and not 0 <= c <= 0xFFFF:
         raise ValueError(f"cstm = {cstm}, expected None or 0 .. 65535")
     pm = msg.data_ptr() if msg_bytes else None
-    fn = lib().ntt_xof_ragged
-    _run("ntt_xof_ragged", (out, msg, off), stream, lambda s: fn(out.data_ptr(), outlen, pm, msg_bytes, off.data_ptr(), nb, a, c, s))
+    pth = _xof_path(path)
+    fn = lib().ntt_xof_ragged_path
+    _run("ntt_xof_ragged", (out, msg, off), stream,
+         lambda s: fn(out.data_ptr(), outlen, pm, msg_bytes, off.data_ptr(), nb, a, c, pth, s))
     return out
 
 
