@@ -14,8 +14,12 @@ from conftest import LARGE_SETS, PARAM_SETS
 # Batches above this are not run by the tests (2^20 polynomials: 4 GiB at
 # n = 1024, the BASELINE batch).  An in-place n = 1024 transform stays on the
 # radix-16 kernels up to the launch-size limit of csrc/ntt_lat.hpp (2^26 - 1
-# polynomials), so its batch kernels are out of the tests' reach; that switch
-# point is pinned by arithmetic (test_family_cells.py::test_launch_size_limit).
+# polynomials), so no batch the tests can allocate reaches its batch kernels
+# through the entry points; that switch point is pinned by arithmetic
+# (test_family_cells.py::test_launch_size_limit), and the kernels themselves
+# (k_ntt_fwd / k_ntt_inv, in place, odd batches included) are launched at small
+# batches by the test-only probe library: tests/test_gpu_family_probe.py::
+# test_batch_kernel_chunks.
 MAX_TEST_BATCH = 1 << 20
 
 
