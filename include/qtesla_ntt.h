@@ -706,6 +706,107 @@ int poly_unpack_ntt(uint32_t *d_out, size_t pstride, uint32_t *d_max /* [batch][
                     const uint8_t *d_in, size_t stride, size_t batch, int k, int bits, int sgn,
                     int neg, int param_set, void *stream);
 
+/* The logic between the steps of a chain, on the device: row tests, selection
+ * and row moves.  With them a restart loop reruns only its rejected messages:
+ * test the attempt's norms into flags (ntt_rows_over), list the accepted rows
+ * and move their results out (ntt_select want 0, ntt_rows_move), list the
+ * rejected rows, raise their nonces and gather their inputs into the next,
+ * smaller batch (ntt_select want 1 with d_bump, ntt_rows_move) -- every other
+ * entry point already takes any batch size and per-message nonces and keys.
+ * The four know no parameter set and no scheme.  Indices and counts are data,
+ * as d_key and d_off are: no value of either makes the device read or write
+ * outside the extents stated below.  All four are asynchronous on `stream`,
+ * never allocate, use no atomics, write every output word with a plain store
+ * of the one thread that owns it, and no workgroup waits on another.
+ * Checks, in this order unless an entry says otherwise (the first defect
+ * decides; all before any GPU work): NTT_ERR_PARAM; batch == 0 (count == 0)
+ * NTT_OK, nothing else is looked at and nothing is written; NTT_ERR_NULL;
+ * NTT_ERR_ALIGN; NTT_ERR_SIZE (more than 2^31 - 1 rows); NTT_ERR_ALIAS.
+ *
+ * ntt_rows_over: a row of maxima against a row of bounds.
+ *   d_vals [batch][m] uint32 (width 32) or uint64 (width 64); d_flag [batch]
+ *   bounds [m] uint64 in HOST memory, read during the call (not kept)
+ *   f_b = OR_j (d_vals[b][j] > bounds[j]), 0 or 1;
+ *   d_flag[b] = accumulate ? d_flag[b] | f_b : f_b
+ * A bound at or above the type's maximum never flags: that is how a column is
+ * skipped (poly_round's norms are [batch][2]; the signer tests column 0 of z's,
+ * and both columns of w's [batch][k][2] as m = 2 k with alternating bounds).
+ * Width 64 is poly_hsum's sums.  With accumulate the other bits of d_flag[b]
+ * are kept; a flag is "set" when it is not 0.
+ *   NTT_ERR_PARAM  width not 32 / 64, m outside 1 .. NTT_ROWS_M_MAX, accumulate
+ *                  not 0 / 1
+ *   NTT_ERR_NULL   d_flag, d_vals, bounds
+ *   NTT_ERR_ALIGN  d_flag 4-byte, d_vals width / 8
+ *   NTT_ERR_SIZE   batch > 2^31 - 1
+ *   NTT_ERR_ALIAS  d_flag's batch words overlap d_vals' batch m width / 8 bytes */
+#define NTT_ROWS_M_MAX 16
+int ntt_rows_over(uint32_t *d_flag, const void *d_vals, int width, int m,
+                  const uint64_t *bounds /* HOST, m entries, read during the call */,
+                  int accumulate, size_t batch, void *stream);
+
+/* ntt_rows_differ: the verifier's c'' == c' test.  f_b = 1 iff the row_bytes
+ * bytes at d_a + b a_stride and at d_b + b b_stride differ anywhere, 0
+ * otherwise; d_flag[b] as ntt_rows_over's, with the same accumulate.  The
+ * strides let a field be read where it lies -- c' at d_sig + zlen with stride
+ * zlen + 32 -- and bytes [row_bytes, stride) of a row are never read.
+ *   NTT_ERR_PARAM  row_bytes not a multiple of 4 or below 4; a stride not a
+ *                  multiple of 4 or below row_bytes; accumulate not 0 / 1
+ *   NTT_ERR_NULL   d_flag, d_a, d_b
+ *   NTT_ERR_ALIGN  any of the three not 4-byte aligned
+ *   NTT_ERR_SIZE   batch > 2^31 - 1
+ *   NTT_ERR_ALIAS  d_flag's batch words overlap either input's extent,
+ *                  (batch - 1) stride + row_bytes (the two inputs may overlap
+ *                  each other) */
+int ntt_rows_differ(uint32_t *d_flag, const uint8_t *d_a, size_t a_stride,
+                    const uint8_t *d_b, size_t b_stride, size_t row_bytes,
+                    int accumulate, size_t batch, void *stream);
+
+/* ntt_select: flags to an ascending index list.  d_idx[0 .. c) is every b <
+ * batch with (d_flag[b] != 0) == want, in ascending order, and d_count[0] = c;
+ * the words d_idx[c .. batch) are not written.  d_bump is NULL or [batch]
+ * uint32: d_bump[b] += 1 for exactly the selected b, in the same launch (the
+ * rejected messages' nonces).  Ascending order is the contract: what a chain
+ * computes for a message then does not depend on which other messages are
+ * live.  One workgroup walks the flags and carries the running offset, so
+ * there is no scratch memory and nothing to wait for; at 2^20 flags it streams
+ * 4 MB through one compute unit (the time is in DESIGN.md section 5r).
+ * batch == 0 writes nothing, d_count included.
+ *   NTT_ERR_PARAM  want not 0 / 1
+ *   NTT_ERR_NULL   d_idx, d_count, d_flag (d_bump may be NULL)
+ *   NTT_ERR_ALIGN  any pointer not 4-byte aligned
+ *   NTT_ERR_SIZE   batch > 2^31 - 1
+ *   NTT_ERR_ALIAS  any two of d_idx's batch words, d_count's one word, d_flag's
+ *                  batch words and d_bump's batch words overlap */
+int ntt_select(uint32_t *d_idx, uint32_t *d_count, const uint32_t *d_flag,
+               int want, uint32_t *d_bump, size_t batch, void *stream);
+
+/* ntt_rows_move: gather and scatter whole rows by index, the count on the
+ * device.  For i < min(count, d_count ? d_count[0] : count), with
+ * si = d_src_idx ? d_src_idx[i] : i and di = d_dst_idx ? d_dst_idx[i] : i:
+ * if si < src_rows and di < dst_rows, the row_bytes bytes at d_src + si
+ * src_stride are copied to d_dst + di dst_stride; otherwise row i is skipped.
+ * The skip is the definition, not an error path: no index and no count makes
+ * the device read or write outside the two extents (rows - 1) stride +
+ * row_bytes, and bytes [row_bytes, stride) of a d_dst row are never written.
+ * Distinct di are the caller's duty (ntt_select's lists are distinct); with
+ * equal di which row ends up there is not defined.  The launch is sized by the
+ * host's count and trimmed by the device's, so a sub-batch moves before the
+ * host knows its size.  With both index lists NULL it is a strided row copy.
+ * Rows move in 16-byte accesses when both bases, both strides and row_bytes
+ * are multiples of 16, in dwords otherwise.
+ *   NTT_ERR_PARAM  row_bytes not a multiple of 4 or below 4; a stride not a
+ *                  multiple of 4 or below row_bytes
+ *   count == 0     NTT_OK, nothing else is looked at
+ *   NTT_ERR_NULL   d_dst, d_src (each of d_dst_idx, d_src_idx, d_count may be
+ *                  NULL)
+ *   NTT_ERR_ALIGN  any pointer not 4-byte aligned
+ *   NTT_ERR_SIZE   count, dst_rows or src_rows > 2^31 - 1
+ *   NTT_ERR_ALIAS  d_dst's extent overlaps d_src's extent, an index list's count
+ *                  words or d_count's word (compaction ping-pongs two buffers) */
+int ntt_rows_move(uint8_t *d_dst, size_t dst_stride, const uint32_t *d_dst_idx, size_t dst_rows,
+                  const uint8_t *d_src, size_t src_stride, const uint32_t *d_src_idx, size_t src_rows,
+                  size_t row_bytes, const uint32_t *d_count, size_t count, void *stream);
+
 /* Nussbaumer negacyclic product (the paper's alternate algorithm): the
  * reference's single-polynomial CPU routine nussbaumer_fft (NTT.cu:167-277,
  * driver test_nussbaumer :1987-2005), batched on the GPU and extended from

@@ -23,6 +23,7 @@
 #include "ntt_mulkl.hpp"
 #include "ntt_pack.hpp"
 #include "ntt_round.hpp"
+#include "ntt_rows.hpp"
 #include "ntt_gauss.hpp"
 #include "ntt_gen_a.hpp"
 #include "ntt_sample.hpp"
@@ -258,6 +259,7 @@ static_assert((int)FWD == (int)LAT_FWD && (int)INV == (int)LAT_INV && (int)FWD_B
                   (int)INV_BR == (int)LAT_INV_BR,
               "switch table order");
 static_assert(MULK_K_MAX == NTT_MUL_K_MAX, "ABI row limit");
+static_assert(ROWS_M_MAX == NTT_ROWS_M_MAX, "ABI column limit of ntt_rows_over");
 static_assert(XOF_RATE128 * 8 == 168 && XOF_RATE256 * 8 == 136 && NTT_XOF_OUT_MAX % 8 == 0, "ABI rates and output limit");
 static_assert(NTT_CHALLENGE_BLOCKS_MAX * CHALLENGE_DRAWS >= 8 * NTT_CHALLENGE_H_MAX, "block bound far above h / (7/8) draws");
 static_assert(MULKL_L_MAX == NTT_MUL_L_MAX && NTT_MUL_L_MAX == 2, "ABI column limit (poly_mul_ntt_kl launches l = 2)");
@@ -625,6 +627,20 @@ template <int PS> struct LHsum {
         return finish_launch();
     }
 };
+
+// ntt_rows_over / _differ / ntt_select / ntt_rows_move (ntt_rows.hpp): bytes of `rows` rows of `row_bytes` at `stride`
+size_t rows_extent(size_t rows, size_t stride, size_t row_bytes) { return rows ? (rows - 1) * stride + row_bytes : 0; }
+
+// log2 of the lanes that share a row of `units` loads: the smallest power of two that covers them, at most 2^max_log
+uint32_t row_lanes_log(size_t units, uint32_t max_log)
+{
+    uint32_t l = 0;
+    while (l < max_log && ((size_t)1 << l) < units) ++l;
+    return l;
+}
+
+// the three grid kernels of ntt_rows.hpp stride over their rows: one workgroup per `per_wg` rows, at most 16 per CU
+dim3 rows_grid(size_t rows, size_t per_wg, const DevInfo &d) { return dim3(capped_grid(rows, per_wg, d.cus, 16)); }
 
 }  // namespace
 
@@ -1065,6 +1081,109 @@ int poly_unpack_ntt(uint32_t *d_out, size_t pstride, uint32_t *d_max, const uint
                         (uint32_t)(((uint64_t)1 << 32) / (uint32_t)bits) + 1u};
     return launch<LUnpackNtt, LARGE_PS0>(ps, d_out, pstride, d_max, (const uint32_t *)d_in, R, neg != 0, batch * k,
                                          (hipStream_t)stream);
+}
+
+int ntt_rows_over(uint32_t *d_flag, const void *d_vals, int width, int m, const uint64_t *bounds, int accumulate, size_t batch,
+                  void *stream)
+{
+    if ((width != 32 && width != 64) || m < 1 || m > NTT_ROWS_M_MAX || (accumulate != 0 && accumulate != 1)) return NTT_ERR_PARAM;
+    if (batch == 0) return NTT_OK;
+    if (!d_flag || !d_vals || !bounds) return NTT_ERR_NULL;
+    if ((((uintptr_t)d_flag) & 3u) || (((uintptr_t)d_vals) & (uintptr_t)(width / 8 - 1))) return NTT_ERR_ALIGN;
+    if (batch > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
+    if (ranges_overlap(d_flag, batch * 4, d_vals, batch * (size_t)m * (size_t)(width / 8))) return NTT_ERR_ALIAS;
+    int rc;
+    DevInfo *d = nullptr;
+    if ((rc = device_ready(&d)) != NTT_OK) return rc;
+    RowBounds rb = {};
+    for (int j = 0; j < m; j++) rb.b[j] = bounds[j];
+    const dim3 grid = rows_grid(batch, ROWS_WG, *d), wg(ROWS_WG);
+    if (width == 32)
+        hipLaunchKernelGGL(k_rows_over<uint32_t>, grid, wg, 0, (hipStream_t)stream, d_flag, (const uint32_t *)d_vals, (uint32_t)m,
+                           rb, (uint32_t)accumulate, (uint32_t)batch);
+    else
+        hipLaunchKernelGGL(k_rows_over<uint64_t>, grid, wg, 0, (hipStream_t)stream, d_flag, (const uint64_t *)d_vals, (uint32_t)m,
+                           rb, (uint32_t)accumulate, (uint32_t)batch);
+    return finish_launch();
+}
+
+int ntt_rows_differ(uint32_t *d_flag, const uint8_t *d_a, size_t a_stride, const uint8_t *d_b, size_t b_stride, size_t row_bytes,
+                    int accumulate, size_t batch, void *stream)
+{
+    if ((row_bytes & 3u) || row_bytes < 4 || ((a_stride | b_stride) & 3u) || a_stride < row_bytes || b_stride < row_bytes)
+        return NTT_ERR_PARAM;
+    if (accumulate != 0 && accumulate != 1) return NTT_ERR_PARAM;
+    if (batch == 0) return NTT_OK;
+    if (!d_flag || !d_a || !d_b) return NTT_ERR_NULL;
+    if ((((uintptr_t)d_flag) | ((uintptr_t)d_a) | ((uintptr_t)d_b)) & 3u) return NTT_ERR_ALIGN;
+    if (batch > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
+    if (ranges_overlap(d_flag, batch * 4, d_a, rows_extent(batch, a_stride, row_bytes)) ||
+        ranges_overlap(d_flag, batch * 4, d_b, rows_extent(batch, b_stride, row_bytes)))
+        return NTT_ERR_ALIAS;
+    int rc;
+    DevInfo *d = nullptr;
+    if ((rc = device_ready(&d)) != NTT_OK) return rc;
+    const uint32_t llpr = row_lanes_log(row_bytes / 4, 6);   // a group never spans two waves
+    hipLaunchKernelGGL(k_rows_differ, rows_grid(batch, ROWS_WG >> llpr, *d), dim3(ROWS_WG), 0, (hipStream_t)stream, d_flag,
+                       (const uint32_t *)d_a, a_stride / 4, (const uint32_t *)d_b, b_stride / 4, row_bytes / 4,
+                       (uint32_t)accumulate, (uint32_t)batch, llpr);
+    return finish_launch();
+}
+
+int ntt_select(uint32_t *d_idx, uint32_t *d_count, const uint32_t *d_flag, int want, uint32_t *d_bump, size_t batch, void *stream)
+{
+    if (want != 0 && want != 1) return NTT_ERR_PARAM;
+    if (batch == 0) return NTT_OK;
+    if (!d_idx || !d_count || !d_flag) return NTT_ERR_NULL;
+    if ((((uintptr_t)d_idx) | ((uintptr_t)d_count) | ((uintptr_t)d_flag) | ((uintptr_t)d_bump)) & 3u) return NTT_ERR_ALIGN;
+    if (batch > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
+    // idx, count, flag and bump: no two of them overlap
+    const void *p[4] = {d_idx, d_count, d_flag, d_bump};
+    const size_t bytes[4] = {batch * 4, 4, batch * 4, batch * 4};
+    for (int i = 0; i < 4; i++)
+        for (int j = i + 1; j < 4; j++)
+            if (p[i] && p[j] && ranges_overlap(p[i], bytes[i], p[j], bytes[j])) return NTT_ERR_ALIAS;
+    int rc;
+    DevInfo *d = nullptr;
+    if ((rc = device_ready(&d)) != NTT_OK) return rc;
+    hipLaunchKernelGGL(k_select, dim3(1), dim3(SELECT_WG), 0, (hipStream_t)stream, d_idx, d_count, d_flag, (uint32_t)want, d_bump,
+                       (uint32_t)batch);
+    return finish_launch();
+}
+
+int ntt_rows_move(uint8_t *d_dst, size_t dst_stride, const uint32_t *d_dst_idx, size_t dst_rows, const uint8_t *d_src,
+                  size_t src_stride, const uint32_t *d_src_idx, size_t src_rows, size_t row_bytes, const uint32_t *d_count,
+                  size_t count, void *stream)
+{
+    if ((row_bytes & 3u) || row_bytes < 4 || ((dst_stride | src_stride) & 3u) || dst_stride < row_bytes || src_stride < row_bytes)
+        return NTT_ERR_PARAM;
+    if (count == 0) return NTT_OK;
+    if (!d_dst || !d_src) return NTT_ERR_NULL;
+    if ((((uintptr_t)d_dst) | ((uintptr_t)d_src) | ((uintptr_t)d_dst_idx) | ((uintptr_t)d_src_idx) | ((uintptr_t)d_count)) & 3u)
+        return NTT_ERR_ALIGN;
+    if (count > (size_t)0x7FFFFFFF || dst_rows > (size_t)0x7FFFFFFF || src_rows > (size_t)0x7FFFFFFF) return NTT_ERR_SIZE;
+    const size_t dbytes = rows_extent(dst_rows, dst_stride, row_bytes);
+    const size_t sbytes = rows_extent(src_rows, src_stride, row_bytes);
+    if (dbytes && ((sbytes && ranges_overlap(d_dst, dbytes, d_src, sbytes)) ||
+                   (d_dst_idx && ranges_overlap(d_dst, dbytes, d_dst_idx, count * 4)) ||
+                   (d_src_idx && ranges_overlap(d_dst, dbytes, d_src_idx, count * 4)) ||
+                   (d_count && ranges_overlap(d_dst, dbytes, d_count, 4))))
+        return NTT_ERR_ALIAS;   // an extent of no rows overlaps nothing
+    int rc;
+    DevInfo *d = nullptr;
+    if ((rc = device_ready(&d)) != NTT_OK) return rc;
+    // 16-byte units when both bases, both strides and the row allow it, dwords otherwise
+    const bool wide = !((((uintptr_t)d_dst) | ((uintptr_t)d_src) | dst_stride | src_stride | row_bytes) & 15u);
+    const size_t units = row_bytes / (wide ? 16 : 4);
+    const uint32_t llpr = row_lanes_log(units, 8);   // at most the workgroup
+    const dim3 grid = rows_grid(count, ROWS_WG >> llpr, *d), wg(ROWS_WG);
+    if (wide)
+        hipLaunchKernelGGL(k_rows_move<uint4>, grid, wg, 0, (hipStream_t)stream, d_dst, dst_stride, d_dst_idx, dst_rows, d_src,
+                           src_stride, d_src_idx, src_rows, units, d_count, (uint32_t)count, llpr);
+    else
+        hipLaunchKernelGGL(k_rows_move<uint32_t>, grid, wg, 0, (hipStream_t)stream, d_dst, dst_stride, d_dst_idx, dst_rows, d_src,
+                           src_stride, d_src_idx, src_rows, units, d_count, (uint32_t)count, llpr);
+    return finish_launch();
 }
 
 int poly_mul_nussbaumer(uint32_t *d_c, const uint32_t *d_a, const uint32_t *d_b, size_t batch, int ps, int ring,

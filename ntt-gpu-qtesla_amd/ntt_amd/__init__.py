@@ -111,7 +111,11 @@ def lib():
         L.poly_unpack.argtypes = [_vp, _vp, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
         L.poly_unpack_ntt.argtypes = [_vp, _sz, _vp, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_int, _vp]
-        L.poly_mul_nussbaumer.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
+        L.ntt_rows_over.argtypes = [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, _sz, _vp]
+        L.ntt_rows_differ.argtypes = [_vp, _vp, _sz, _vp, _sz, _sz, ctypes.c_int, _sz, _vp]
+        L.ntt_select.argtypes = [_vp, _vp, _vp, ctypes.c_int, _vp, _sz, _vp]
+        L.ntt_rows_move.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp]
+        L.poly_mul_nussbaumer.argtypes =[_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
         L.ntt_fill_uniform.argtypes = [_vp, _sz, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, _vp]
         L.ntt_last_hip_error.restype = ctypes.c_int
         L.ntt_strerror.restype = ctypes.c_char_p
@@ -1046,6 +1050,142 @@ def poly_unpack_ntt(out, inp, param_set, bits: int, k: int, signed=False, negate
          lambda s: fn(out.data_ptr(), pstride, pm, inp.data_ptr(), stride, nb, k, int(bits), sgn, 1 if negate else 0,
                       _ps(param_set), s))
     return out, maxima
+
+
+ROWS_M_MAX = 16   # NTT_ROWS_M_MAX
+
+
+def _words(name: str, t, numel=None):
+    """A contiguous 1-D int32/uint32 tensor (of `numel` elements): flags, index lists, counts."""
+    _torch()
+    if t.dtype not in _INT_DTYPES:
+        raise TypeError(f"{name}: expected int32/uint32 storage, got {t.dtype}")
+    if t.dim() != 1 or (numel is not None and t.numel() != numel):
+        raise ValueError(f"{name}: shape {tuple(t.shape)}, expected [{'.' if numel is None else numel}]")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: tensor must be contiguous")
+    return t
+
+
+def _strided_rows(name: str, t):
+    """(rows, row bytes, stride in bytes) of a tensor [rows, ...] whose rows are
+    contiguous in themselves and lie a fixed, non-negative distance apart: a
+    contiguous tensor, or a view of some columns of one (sig[:, zlen:])."""
+    if t.dim() < 1:
+        raise ValueError(f"{name}: shape {tuple(t.shape)}, expected [rows, ...]")
+    inner = 1   # elements per row
+    for size, st in zip(reversed(t.shape[1:]), reversed(t.stride()[1:])):
+        if size != 1 and st != inner:
+            raise ValueError(f"{name}: strides {t.stride()}: a row must be contiguous in itself")
+        inner *= size
+    item = t.element_size()
+    row_bytes = inner * item
+    if row_bytes % 4 or row_bytes < 4:
+        raise ValueError(f"{name}: {row_bytes} bytes per row, expected a multiple of 4, at least 4")
+    stride = t.stride(0) * item if t.shape[0] > 1 else row_bytes
+    if stride % 4 or stride < row_bytes:
+        raise ValueError(f"{name}: rows {stride} bytes apart, expected a multiple of 4, at least the row's {row_bytes}")
+    return t.shape[0], row_bytes, stride
+
+
+def rows_over(flag, vals, bounds, accumulate=False, stream=None):
+    """flag[b] = any(vals[b][j] > bounds[j]), or flag[b] | that with accumulate
+    (ntt_rows_over).  vals is a contiguous [batch, ...] device tensor of int32 /
+    uint32 (poly_round's norms, poly_unpack's maxima) or int64 (poly_hsum's
+    sums), its bits taken as unsigned, with m = 1 .. 16 values per row; bounds a
+    sequence of m Python ints in 0 .. 2^64 - 1 -- one at or above the type's
+    maximum never flags, which skips its column; flag int32 [batch].  Returns
+    flag."""
+    torch = _torch()
+    if vals.dtype in _INT_DTYPES:
+        width = 32
+    elif vals.dtype in (torch.int64, getattr(torch, "uint64", torch.int64)):
+        width = 64
+    else:
+        raise TypeError(f"vals: expected int32/uint32 or int64 storage, got {vals.dtype}")
+    if vals.dim() < 1 or not vals.is_contiguous():
+        raise ValueError(f"vals: shape {tuple(vals.shape)}, expected a contiguous [batch, ...]")
+    nb = vals.shape[0]
+    _words("flag", flag, nb)
+    bounds = [int(x) for x in bounds]
+    m = len(bounds)
+    if not 1 <= m <= ROWS_M_MAX:
+        raise ValueError(f"{m} bounds, expected 1 .. {ROWS_M_MAX}")
+    if vals.numel() != nb * m:
+        raise ValueError(f"vals: shape {tuple(vals.shape)} with {m} bounds, expected {m} values per row")
+    if any(not 0 <= x < 1 << 64 for x in bounds):
+        raise ValueError("bounds: expected 0 .. 2^64 - 1")
+    arr = (ctypes.c_uint64 * m)(*bounds)
+    fn = lib().ntt_rows_over
+    _run("ntt_rows_over", (flag, vals), stream,
+         lambda s: fn(flag.data_ptr(), vals.data_ptr(), width, m, arr, 1 if accumulate else 0, nb, s))
+    return flag
+
+
+def rows_differ(flag, a, b, accumulate=False, stream=None):
+    """flag[r] = 1 iff rows a[r] and b[r] differ in any byte, or flag[r] | that
+    with accumulate (ntt_rows_differ).  a and b are [batch, ...] device tensors
+    of equal bytes per row (a multiple of 4), each contiguous or a view of some
+    columns of a contiguous tensor, read where it lies (c' as sig[:, zlen:]);
+    flag int32 [batch].  Returns flag."""
+    na, row_bytes, sa = _strided_rows("a", a)
+    nb, row_b, sb = _strided_rows("b", b)
+    if na != nb or row_bytes != row_b:
+        raise ValueError(f"a / b: {na} rows of {row_bytes} bytes and {nb} rows of {row_b} bytes")
+    _words("flag", flag, nb)
+    fn = lib().ntt_rows_differ
+    _run("ntt_rows_differ", (flag, a, b), stream,
+         lambda s: fn(flag.data_ptr(), a.data_ptr(), sa, b.data_ptr(), sb, row_bytes, 1 if accumulate else 0, nb, s))
+    return flag
+
+
+def select(idx, count, flag, want, bump=None, stream=None):
+    """idx[:c] = the b with (flag[b] != 0) == want, ascending, and count[0] = c
+    (ntt_select); idx[c:] keeps what it held.  bump, int32 [batch] or None, is
+    raised by one at exactly the selected b.  idx and flag are int32 [batch],
+    count int32 [1]; want is False / True.  An empty batch writes nothing,
+    count included.  Returns (idx, count)."""
+    nb = _words("flag", flag).numel()
+    _words("idx", idx, nb)
+    _words("count", count, 1)
+    if want not in (0, 1, False, True):
+        raise ValueError(f"want = {want!r}, expected False / True")
+    tensors, pb = (idx, count, flag), None
+    if bump is not None:
+        tensors, pb = (idx, count, flag, _words("bump", bump, nb)), bump.data_ptr()
+    fn = lib().ntt_select
+    _run("ntt_select", tensors, stream, lambda s: fn(idx.data_ptr(), count.data_ptr(), flag.data_ptr(), int(want), pb, nb, s))
+    return idx, count
+
+
+def rows_move(dst, src, dst_idx=None, src_idx=None, count=None, n=None, stream=None):
+    """dst[dst_idx[i]] = src[src_idx[i]] for i < min(n, count[0]), whole rows
+    (ntt_rows_move).  dst and src are [rows, ...] device tensors of equal bytes
+    per row (a multiple of 4; the dtypes need not match), each contiguous or a
+    view of some columns of a contiguous tensor; a 1-D tensor has one element
+    per row.  dst_idx / src_idx are int32 index lists or None (the identity);
+    an index at or past its side's rows skips the row.  count is an int32 [1]
+    device tensor or None; n, the host's count that sizes the launch, defaults
+    to the index lists' length, or without lists to the smaller side's rows.
+    Returns dst."""
+    dr, row_bytes, ds = _strided_rows("dst", dst)
+    sr, row_s, ss = _strided_rows("src", src)
+    if row_bytes != row_s:
+        raise ValueError(f"dst / src: rows of {row_bytes} and of {row_s} bytes")
+    lists = [(nm, _words(nm, t)) for nm, t in (("dst_idx", dst_idx), ("src_idx", src_idx)) if t is not None]
+    if n is None:
+        n = min(t.numel() for _, t in lists) if lists else min(dr, sr)
+    n = int(n)
+    if n < 0 or any(t.numel() < n for _, t in lists):
+        raise ValueError(f"n = {n} with index lists of {[t.numel() for _, t in lists]} entries")
+    if count is not None:
+        _words("count", count, 1)
+    tensors = (dst, src) + tuple(t for _, t in lists) + (() if count is None else (count,))
+    pd, psrc, pc = (None if t is None else t.data_ptr() for t in (dst_idx, src_idx, count))
+    fn = lib().ntt_rows_move
+    _run("ntt_rows_move", tensors, stream,
+         lambda s: fn(dst.data_ptr(), ds, pd, dr, src.data_ptr(), ss, psrc, sr, row_bytes, pc, n, s))
+    return dst
 
 
 def poly_mul_nussbaumer(c, a, b, param_set, ring="q", stream=None):
