@@ -22,118 +22,11 @@ one) and, by default, on that device's current stream.
 from __future__ import annotations
 
 import ctypes
-import os
 
 import numpy as np
 
-PKG_DIR = os.path.dirname(os.path.abspath(__file__))
-ROOT_DIR = os.path.dirname(PKG_DIR)
-LIB_PATH = os.environ.get("NTT_AMD_LIB") or os.path.join(ROOT_DIR, "lib", "libqtesla_ntt.so")
-HEADER_PATH = os.path.join(os.path.dirname(ROOT_DIR), "include", "qtesla_ntt.h")
-
-PARAM_SETS = {"ref": 0, "p-I": 1, "p-III": 2, "p-III-4096": 3, "p-III-8192": 4}
-
-NTT_OK = 0
-NTT_ERR_PARAM = -1
-NTT_ERR_NULL = -2
-NTT_ERR_ALIGN = -3
-NTT_ERR_HIP = -4
-NTT_ERR_SIZE = -5
-NTT_ERR_ALIAS = -6
-
-RINGS = {"q": 0, "m32": 1}   # NTT_RING_Q, NTT_RING_M32
-
-
-class NTTError(RuntimeError):
-    def __init__(self, code: int, where: str):
-        self.code = code
-        msg = lib().ntt_strerror(code).decode()
-        if code == NTT_ERR_HIP:
-            msg += f" (hipError {lib().ntt_last_hip_error()})"
-        super().__init__(f"{where}: {msg} [{code}]")
-
-
-_lib = None
-_u32p = ctypes.POINTER(ctypes.c_uint32)
-_vp = ctypes.c_void_p
-_sz = ctypes.c_size_t
-
-
-def lib():
-    """Load libqtesla_ntt.so (raises if it has not been built)."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                f"HIP library {LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
-        # One HIP runtime per process: torch ships its own libamdhip64, loaded
-        # into the global scope when torch is imported.  Importing it first
-        # makes this library's hip* references bind to that same runtime; a
-        # second runtime initialised after torch's finds no device
-        # (hipErrorNoDevice from the host-buffer context, measured).
-        try:
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        L = ctypes.CDLL(LIB_PATH)
-        L.ntt_param_info.argtypes = [ctypes.c_int] + [_u32p] * 6
-        L.ntt_get_tables.argtypes = [ctypes.c_int] + [_u32p] * 5
-        for nm in ("poly_ntt", "poly_invntt"):
-            getattr(L, nm).argtypes = [_vp, _vp, _sz, ctypes.c_int, _vp]
-        for nm in ("poly_ntt_oop", "poly_invntt_oop", "poly_bitrev_copy", "poly_ntt_bitrev", "poly_invntt_bitrev"):
-            getattr(L, nm).argtypes = [_vp, _vp, _sz, ctypes.c_int, _vp]
-        for nm in ("poly_mul", "poly_mul_ntt", "poly_pointwise"):
-            getattr(L, nm).argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, _vp]
-        L.poly_mul_ntt_k.argtypes = [_vp, _vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
-        L.ntt_mul_k_shape.argtypes = [ctypes.c_int, ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_int)]
-        L.poly_mul_ntt_kl.argtypes = [_vp, ctypes.POINTER(_vp), _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
-        L.ntt_mul_kl_shape.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_int)]
-        L.poly_scatter.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
-        L.poly_round.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
-        L.poly_mul_ntt_kl_round.argtypes = [_vp, _vp, ctypes.POINTER(_vp), _vp, _vp, _sz, ctypes.c_int, ctypes.c_int,
-                                            ctypes.c_int, ctypes.c_int, _vp]
-        L.poly_mul_ntt_kl_keyed.argtypes = [_vp, ctypes.POINTER(_vp), _vp, _vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_int,
-                                            ctypes.c_int, _vp]
-        L.poly_mul_ntt_kl_round_keyed.argtypes = [_vp, _vp, ctypes.POINTER(_vp), _vp, _vp, _sz, _vp, _sz, ctypes.c_int,
-                                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
-        L.ntt_xof.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, _vp]
-        L.ntt_xof_ragged.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
-        L.ntt_xof_path.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
-        L.ntt_xof_ragged_path.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
-        L.ntt_xof_small_batch_max.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(_sz)]
-        L.poly_challenge.argtypes = [_vp, _vp, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, _vp]
-        L.poly_sample_y.argtypes = [_vp, _vp, _sz, _vp, ctypes.c_uint32, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
-        L.poly_gen_a.argtypes = [_vp, _sz, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
-        L.poly_sample_gauss.argtypes = [_vp, _vp, _sz, _vp, ctypes.c_uint32, _vp, ctypes.c_int, ctypes.c_int, _sz, ctypes.c_int,
-                                        ctypes.c_int, _vp]
-        L.poly_hsum.argtypes = [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
-        L.poly_pack.argtypes = [_vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
-        L.poly_unpack.argtypes = [_vp, _vp, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
-        L.poly_unpack_ntt.argtypes = [_vp, _sz, _vp, _vp, _sz, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                      ctypes.c_int, _vp]
-        L.ntt_rows_over.argtypes = [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, _sz, _vp]
-        L.ntt_rows_differ.argtypes = [_vp, _vp, _sz, _vp, _sz, _sz, ctypes.c_int, _sz, _vp]
-        L.ntt_select.argtypes = [_vp, _vp, _vp, ctypes.c_int, _vp, _sz, _vp]
-        L.ntt_rows_move.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp]
-        L.poly_mul_nussbaumer.argtypes =[_vp, _vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp]
-        L.ntt_fill_uniform.argtypes = [_vp, _sz, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, _vp]
-        L.ntt_last_hip_error.restype = ctypes.c_int
-        L.ntt_strerror.restype = ctypes.c_char_p
-        L.ntt_strerror.argtypes = [ctypes.c_int]
-        L.ntt_build_info.argtypes = [ctypes.c_char_p, _sz]
-        L.ntt_sync_expiries.argtypes = [_u32p]
-        L.ntt_small_batch_max.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(_sz)]
-        L.ntt_small_batch_radix.argtypes = [ctypes.c_int, ctypes.c_int, _sz, ctypes.POINTER(ctypes.c_int)]
-        L.ntt_host_ctx_create.argtypes = [ctypes.POINTER(_vp), ctypes.c_int, _sz, ctypes.c_int]
-        L.ntt_host_ctx_destroy.argtypes = [_vp]
-        for nm in ("poly_ntt_host", "poly_invntt_host"):
-            getattr(L, nm).argtypes = [_vp, _vp, _vp, _sz]
-        L.poly_mul_host.argtypes = [_vp, _vp, _vp, _vp, _sz]
-        L.ntt_host_alloc.argtypes = [_sz]
-        L.ntt_host_alloc.restype = _vp
-        L.ntt_host_free.argtypes = [_vp]
-        _lib = L
-    return _lib
+from ._abi import *  # noqa: F401,F403 -- paths, constants, SIGNATURES, lib, NTTError: this package's names too
+from ._abi import _FN, _sz, _u32p, _vp
 
 
 def _ps(param_set) -> int:
@@ -185,10 +78,6 @@ def sync_expiries() -> int:
     return v.value
 
 
-# entry points of the small-batch switch (NTT_OP_* in qtesla_ntt.h)
-SWITCH_OPS = {"fwd": 0, "inv": 1, "fwd_br": 2, "inv_br": 3, "mul": 4, "mul_ntt": 5, "fwd_oop": 6, "inv_oop": 7}
-
-
 def small_batch_max(param_set, op: str) -> int:
     """Largest batch for which entry point `op` (a SWITCH_OPS key) runs the
     small-batch kernels, one polynomial per workgroup (0: never)."""
@@ -217,61 +106,57 @@ def build_hash() -> str:
     return info.rsplit("src=", 1)[1].strip() if "src=" in info else "unknown"
 
 
-# ---------------------------------------------------------------- raw API
-# device pointers as ints, stream as int (hipStream_t) or None
-
-def raw_poly_ntt(ptr: int, batch: int, param_set, stream=None):
-    _check(lib().poly_ntt(ptr, None, batch, _ps(param_set), stream), "poly_ntt")
-
-
-def raw_poly_invntt(ptr: int, batch: int, param_set, stream=None):
-    _check(lib().poly_invntt(ptr, None, batch, _ps(param_set), stream), "poly_invntt")
-
-
-def raw_poly_mul(c: int, a: int, b: int, batch: int, param_set, stream=None):
-    _check(lib().poly_mul(c, a, b, batch, _ps(param_set), stream), "poly_mul")
-
-
 # ------------------------------------------------------------- torch API
 
 _TORCH = None
 _INT_DTYPES = ()
+_BYTE_DTYPES = ()
+_RAW_STREAM = None
 
 
 def _torch():
     """torch, imported on first use (this module also serves torch-free
     ctypes callers) and then cached: the per-call wrappers below run once per
     polynomial in the signing loop's small calls."""
-    global _TORCH, _INT_DTYPES
+    global _TORCH, _INT_DTYPES, _BYTE_DTYPES, _RAW_STREAM
     if _TORCH is None:
         import torch
         _INT_DTYPES = (torch.int32, getattr(torch, "uint32", torch.int32))
+        _BYTE_DTYPES = (torch.int8, torch.uint8)
+        # torch's raw accessor where this torch build has it (no Stream
+        # object: ~1.4 us less per call, tools/call_overhead.py)
+        _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
         _TORCH = torch
     return _TORCH
 
 
-def _device_of(*tensors):
-    """The one device all operands live on (ValueError otherwise)."""
-    if len(tensors) == 1 and getattr(tensors[0], "is_cuda", False):
-        return tensors[0].device
+def _same_device(tensors):
+    """All operands (None: an optional one not given) live on one device
+    (ValueError otherwise)."""
     dev = None
     for t in tensors:
+        if t is None:
+            continue
         if not getattr(t, "is_cuda", False):
             raise ValueError("ntt_amd operates on device tensors only (no CPU fallback)")
         if dev is None:
             dev = t.device
         elif t.device != dev:
             raise ValueError(f"operands on different devices: {dev} and {t.device}")
-    return dev
 
 
 def _stream(stream, device=None):
-    if stream is None:
+    """The stream's handle (hipStream_t) as an int: of a torch Stream or an
+    int as given, of None `device`'s current stream (a torch.device, an
+    index, or None for the current device)."""
+    if stream is not None:
+        return getattr(stream, "cuda_stream", stream)
+    if type(device) is not int:
         torch = _torch()
         if isinstance(device, torch.device) and device.index is not None:
-            return _current_raw_stream(device.index)
+            return _stream(None, device.index)
         return torch.cuda.current_stream(device).cuda_stream
-    return getattr(stream, "cuda_stream", stream)
+    return _RAW_STREAM(device) if _RAW_STREAM is not None else _torch().cuda.current_stream(device).cuda_stream
 
 
 def _batch(t, n: int, dtypes=None, storage="int32/uint32") -> int:
@@ -288,15 +173,41 @@ def _batch(t, n: int, dtypes=None, storage="int32/uint32") -> int:
     return numel // n
 
 
-def _run(where: str, tensors, stream, call):
-    """Check the operands, make their device current and call `call(stream)`."""
-    dev = _device_of(*tensors)
+def _byte_batch(t) -> int:
+    """_batch of an int8/uint8 tensor in bytes."""
+    _torch()
+    return _batch(t, 1, _BYTE_DTYPES, "int8/uint8")
+
+
+def _run(name: str, tensors, stream, *args):
+    """The call path of the device entry points (_inplace runs the same steps
+    in line for the in-place transforms): check that the operands
+    (None: an optional one not given) share a device, make it current unless
+    it is, and call the ABI's `name` as fn(*args, stream) -- each of them takes
+    the stream last.  An error names the entry point less its "_path" suffix
+    (ntt_xof_path is how ntt_xof is called)."""
+    t = tensors[0]
+    if len(tensors) > 1 or not getattr(t, "is_cuda", False):
+        _same_device(tensors)
     torch = _TORCH or _torch()
-    if torch.cuda.current_device() == dev.index:   # already current: no device switch
-        _check(call(_stream(stream, dev)), where)
-        return
-    with torch.cuda.device(dev):
-        _check(call(_stream(stream, dev)), where)
+    dev = t.get_device()   # an int: no torch.device object
+    fn = _FN.get(name)
+    if fn is None:
+        lib()
+        fn = _FN[name]
+    s = _stream(stream, dev)
+    if torch.cuda.current_device() == dev:   # already current: no device switch
+        rc = fn(*args, s)
+    else:
+        with torch.cuda.device(dev):
+            rc = fn(*args, s)
+    if rc != NTT_OK:
+        raise NTTError(rc, name.removesuffix("_path"))
+
+
+def _ptr(t):
+    """The device pointer of an optional operand (None: NULL)."""
+    return None if t is None else t.data_ptr()
 
 
 def _same_batch(n: int, first, *others) -> int:
@@ -308,48 +219,31 @@ def _same_batch(n: int, first, *others) -> int:
 
 
 def _inplace(name: str, t, param_set, stream):
-    """The in-place transforms' call path, the signing loop's one-polynomial
-    calls (config 1): the same checks as _batch / _run with fewer
-    interpreter steps -- the device as an int (no torch.device object), no
-    closure, the ctypes function looked up once -- 5.3 -> ~4 us per call
-    against 3.25 us for a bare ctypes call (tools/call_overhead.py)."""
-    n = _N_CACHE.get(param_set)
-    if n is None:
-        n = _n(param_set)
-    torch = _TORCH or _torch()
-    if not t.is_cuda or t.dtype not in _INT_DTYPES or not t.is_contiguous():
-        _batch(t, n)   # raises the specific error
+    """The in-place transforms, the signing loop's one-polynomial calls
+    (config 1): _batch's checks in one test, _batch itself only for its error
+    text, and _run's steps for its one tensor in line, with _run's _stream --
+    through _run itself bench config 1 lost ~0.3 of its ~4.2 us per call
+    (profiles/binding_call_path/)."""
+    n = _N_CACHE.get(param_set) or _n(param_set)
     numel = t.numel()
-    if numel % n:
-        _batch(t, n)
+    if not t.is_cuda or t.dtype not in _INT_DTYPES or not t.is_contiguous() or numel % n:
+        _batch(t, n)   # raises the specific error; passes once, before torch is cached
+    torch = _TORCH or _torch()
     fn = _FN.get(name)
     if fn is None:
-        fn = _FN[name] = getattr(lib(), name)
+        lib()
+        fn = _FN[name]
     ps = PARAM_SETS[param_set] if isinstance(param_set, str) else int(param_set)
     dev = t.get_device()
+    s = _stream(stream, dev)
     if torch.cuda.current_device() == dev:
-        s = _current_raw_stream(dev) if stream is None else getattr(stream, "cuda_stream", stream)
         rc = fn(t.data_ptr(), None, numel // n, ps, s)
     else:
         with torch.cuda.device(dev):
-            s = _current_raw_stream(dev) if stream is None else getattr(stream, "cuda_stream", stream)
             rc = fn(t.data_ptr(), None, numel // n, ps, s)
     if rc != NTT_OK:
         raise NTTError(rc, name)
     return t
-
-
-_FN: dict = {}
-
-
-def _current_raw_stream(dev: int):
-    """The device's current stream handle as an int: torch's raw accessor
-    where this torch build has it (no Stream object: ~1.4 us less per call,
-    tools/call_overhead.py), else the public current_stream()."""
-    raw = getattr(_TORCH._C, "_cuda_getCurrentRawStream", None)
-    if raw is not None:
-        return raw(dev)
-    return _TORCH.cuda.current_stream(dev).cuda_stream
 
 
 def poly_ntt(t, param_set, stream=None):
@@ -365,8 +259,7 @@ def poly_invntt(t, param_set, stream=None):
 def _oop(name, out, inp, param_set, stream):
     n = _n(param_set)
     b = _same_batch(n, inp, out)
-    fn = getattr(lib(), name)
-    _run(name, (out, inp), stream, lambda s: fn(out.data_ptr(), inp.data_ptr(), b, _ps(param_set), s))
+    _run(name, (out, inp), stream, out.data_ptr(), inp.data_ptr(), b, _ps(param_set))
     return out
 
 
@@ -396,9 +289,7 @@ def poly_bitrev_copy(out, inp, param_set, stream=None):
 def _mul(name, c, a, b, param_set, stream, *extra):
     n = _n(param_set)
     nb = _same_batch(n, a, b, c)
-    fn = getattr(lib(), name)
-    _run(name, (c, a, b), stream,
-         lambda s: fn(c.data_ptr(), a.data_ptr(), b.data_ptr(), nb, _ps(param_set), *extra, s))
+    _run(name, (c, a, b), stream, c.data_ptr(), a.data_ptr(), b.data_ptr(), nb, _ps(param_set), *extra)
     return c
 
 
@@ -410,9 +301,6 @@ def poly_mul(c, a, b, param_set, stream=None):
 def poly_mul_ntt(c, a, bhat, param_set, stream=None):
     """c = a*b mod (x^n + 1, q) with bhat = poly_ntt(b) given (NTT domain)."""
     return _mul("poly_mul_ntt", c, a, bhat, param_set, stream)
-
-
-MUL_K_MAX = 8   # NTT_MUL_K_MAX
 
 
 def poly_mul_ntt_k(out, y, ahat, param_set, add=None, stream=None):
@@ -432,13 +320,10 @@ def poly_mul_ntt_k(out, y, ahat, param_set, add=None, stream=None):
         raise ValueError(f"out: numel {out.numel()} is not batch*k*n = {nb}*{k}*{n}")
     if add is not None and add.numel() != nb * k * n:
         raise ValueError(f"add: numel {add.numel()} is not batch*k*n = {nb}*{k}*{n}")
-    tensors = (out, y, ahat) if add is None else (out, y, ahat, add)
-    for t in tensors:
+    for t in (out, y, ahat) if add is None else (out, y, ahat, add):
         _batch(t, n)   # device, dtype, contiguity
-    fn = lib().poly_mul_ntt_k
-    pa = None if add is None else add.data_ptr()
-    _run("poly_mul_ntt_k", tensors, stream,
-         lambda s: fn(out.data_ptr(), y.data_ptr(), ahat.data_ptr(), pa, nb, k, _ps(param_set), s))
+    _run("poly_mul_ntt_k", (out, y, ahat, add), stream,
+         out.data_ptr(), y.data_ptr(), ahat.data_ptr(), _ptr(add), nb, k, _ps(param_set))
     return out
 
 
@@ -452,9 +337,6 @@ def mul_k_shape(param_set) -> dict:
     return {"split_max": v.value, "waves": w.value}
 
 
-MUL_L_MAX = 2   # NTT_MUL_L_MAX
-
-
 def poly_mul_ntt_kl(out, ys, ahat, param_set, add=None, stream=None):
     """out[b, i] = sum_j a_ij * ys[j][b] (+ add[b, i]) mod (x^n + 1, q) for the
     k x l matrix ahat[i, j] = poly_ntt(a_ij), shared by the whole batch: one
@@ -466,9 +348,7 @@ def poly_mul_ntt_kl(out, ys, ahat, param_set, add=None, stream=None):
     used where they lie), ahat [k, l, n] with k = ahat.numel() // (l * n), out
     and add [batch, k, n]; add may be out (accumulate in place)."""
     py, pa, nb, k, l, tensors = _rows_operands(_n(param_set), ys, ahat, add, out)
-    fn = lib().poly_mul_ntt_kl
-    _run("poly_mul_ntt_kl", tensors, stream,
-         lambda s: fn(out.data_ptr(), py, ahat.data_ptr(), pa, nb, k, l, _ps(param_set), s))
+    _run("poly_mul_ntt_kl", tensors, stream, out.data_ptr(), py, ahat.data_ptr(), pa, nb, k, l, _ps(param_set))
     return out
 
 
@@ -495,7 +375,7 @@ def _rows_operands(n: int, ys, ahat, add, out=None):
     for t in tensors:
         _batch(t, n)   # device, dtype, contiguity
     py = (_vp * l)(*[y.data_ptr() for y in ys])
-    return py, None if add is None else add.data_ptr(), nb, k, l, tensors
+    return py, _ptr(add), nb, k, l, tensors
 
 
 def mul_kl_shape(param_set, l: int) -> dict:
@@ -521,34 +401,24 @@ def poly_scatter(out, pos, val, param_set, stream=None):
         raise ValueError(f"pos: numel {pos.numel()} is not batch*h = {nb}*h with 1 <= h <= {n}")
     if val.numel() != pos.numel():
         raise ValueError(f"val: numel {val.numel()} is not pos.numel() = {pos.numel()}")
-    tensors = (out, pos, val)
-    for t in tensors:
+    for t in (out, pos, val):
         _batch(t, 1)   # device, dtype, contiguity
-    fn = lib().poly_scatter
-    _run("poly_scatter", tensors, stream,
-         lambda s: fn(out.data_ptr(), pos.data_ptr(), val.data_ptr(), nb, h, _ps(param_set), s))
+    _run("poly_scatter", (out, pos, val), stream, out.data_ptr(), pos.data_ptr(), val.data_ptr(), nb, h, _ps(param_set))
     return out
 
 
 def _round_outputs(where: str, hi, norms, npoly: int, n: int, d: int):
-    """poly_round's outputs: hi int8/uint8 [npoly, n] or None, norms int32
-    [npoly, 2] or None, not both None; the tensors given, for _run."""
-    torch = _torch()
+    """poly_round's outputs, checked: hi int8/uint8 [npoly, n] or None, norms
+    int32 [npoly, 2] or None, not both None.  Returns their two pointers."""
     if hi is None and norms is None:
         raise ValueError(f"{where}: neither hi nor norms given")
     if not 1 <= int(d) <= 30:
         raise ValueError(f"{where}: d = {d}, expected 1 .. 30")
-    outs = []
-    if hi is not None:
-        if _batch(hi, 1, (torch.int8, torch.uint8), "int8/uint8") != npoly * n:   # device, dtype, contiguity
-            raise ValueError(f"hi: numel {hi.numel()} is not polynomials*n = {npoly}*{n}")
-        outs.append(hi)
-    if norms is not None:
-        _batch(norms, 1)   # device, dtype, contiguity
-        if norms.numel() != npoly * 2:
-            raise ValueError(f"norms: numel {norms.numel()} is not polynomials*2 = {npoly}*2")
-        outs.append(norms)
-    return outs
+    if hi is not None and _byte_batch(hi) != npoly * n:   # device, dtype, contiguity
+        raise ValueError(f"hi: numel {hi.numel()} is not polynomials*n = {npoly}*{n}")
+    if norms is not None and _batch(norms, 1) != npoly * 2:   # device, dtype, contiguity
+        raise ValueError(f"norms: numel {norms.numel()} is not polynomials*2 = {npoly}*2")
+    return _ptr(hi), _ptr(norms)
 
 
 def poly_round(w, param_set, d: int, hi=None, norms=None, stream=None):
@@ -564,11 +434,8 @@ def poly_round(w, param_set, d: int, hi=None, norms=None, stream=None):
     within a signed byte (NTTError otherwise).  Returns (hi, norms)."""
     n = _n(param_set)
     nb = _batch(w, n)
-    outs = _round_outputs("poly_round", hi, norms, nb, n, d)
-    fn = lib().poly_round
-    ph = None if hi is None else hi.data_ptr()
-    pn = None if norms is None else norms.data_ptr()
-    _run("poly_round", (w, *outs), stream, lambda s: fn(ph, pn, w.data_ptr(), nb, int(d), _ps(param_set), s))
+    ph, pn = _round_outputs("poly_round", hi, norms, nb, n, d)
+    _run("poly_round", (w, hi, norms), stream, ph, pn, w.data_ptr(), nb, int(d), _ps(param_set))
     return hi, norms
 
 
@@ -581,16 +448,10 @@ def poly_mul_ntt_kl_round(ys, ahat, param_set, d: int, hi=None, norms=None, add=
     may overlap an input.  Returns (hi, norms)."""
     n = _n(param_set)
     py, pa, nb, k, l, ins = _rows_operands(n, ys, ahat, add)
-    outs = _round_outputs("poly_mul_ntt_kl_round", hi, norms, nb * k, n, d)
-    fn = lib().poly_mul_ntt_kl_round
-    ph = None if hi is None else hi.data_ptr()
-    pn = None if norms is None else norms.data_ptr()
-    _run("poly_mul_ntt_kl_round", (*ins, *outs), stream,
-         lambda s: fn(ph, pn, py, ahat.data_ptr(), pa, nb, k, l, int(d), _ps(param_set), s))
+    ph, pn = _round_outputs("poly_mul_ntt_kl_round", hi, norms, nb * k, n, d)
+    _run("poly_mul_ntt_kl_round", (*ins, hi, norms), stream,
+         ph, pn, py, ahat.data_ptr(), pa, nb, k, l, int(d), _ps(param_set))
     return hi, norms
-
-
-MUL_KEYS_MAX = 2**31 - 1   # NTT_MUL_KEYS_MAX
 
 
 def _keyed_operands(n: int, ys, ahat, keys, add, out=None):
@@ -613,11 +474,9 @@ def _keyed_operands(n: int, ys, ahat, keys, add, out=None):
         if keys.dim() != 1 or not ys or keys.shape[0] != ys[0].numel() // n:
             raise ValueError(f"keys: shape {tuple(keys.shape)}, expected [batch]")
     py, pa, nb, k, l, tensors = _rows_operands(n, ys, ahat[0], add, out)
-    pk = None
     if keys is not None:
         _batch(keys, 1)   # device, contiguity
-        tensors, pk = (*tensors, keys), keys.data_ptr()
-    return py, pa, nb, k, l, tensors, pk, nkeys
+    return py, pa, nb, k, l, (*tensors, keys), _ptr(keys), nkeys
 
 
 def poly_mul_ntt_kl_keyed(out, ys, ahat, keys, param_set, add=None, stream=None):
@@ -631,9 +490,8 @@ def poly_mul_ntt_kl_keyed(out, ys, ahat, keys, param_set, add=None, stream=None)
     the last key, a caller's bug, gives the last key's result) or None.  ys,
     add and out as poly_mul_ntt_kl.  Returns out."""
     py, pa, nb, k, l, tensors, pk, nkeys = _keyed_operands(_n(param_set), ys, ahat, keys, add, out)
-    fn = lib().poly_mul_ntt_kl_keyed
     _run("poly_mul_ntt_kl_keyed", tensors, stream,
-         lambda s: fn(out.data_ptr(), py, ahat.data_ptr(), pk, nkeys, pa, nb, k, l, _ps(param_set), s))
+         out.data_ptr(), py, ahat.data_ptr(), pk, nkeys, pa, nb, k, l, _ps(param_set))
     return out
 
 
@@ -644,31 +502,15 @@ def poly_mul_ntt_kl_round_keyed(ys, ahat, keys, param_set, d: int, hi=None, norm
     Returns (hi, norms)."""
     n = _n(param_set)
     py, pa, nb, k, l, ins, pk, nkeys = _keyed_operands(n, ys, ahat, keys, add)
-    outs = _round_outputs("poly_mul_ntt_kl_round_keyed", hi, norms, nb * k, n, d)
-    fn = lib().poly_mul_ntt_kl_round_keyed
-    ph = None if hi is None else hi.data_ptr()
-    pn = None if norms is None else norms.data_ptr()
-    _run("poly_mul_ntt_kl_round_keyed", (*ins, *outs), stream,
-         lambda s: fn(ph, pn, py, ahat.data_ptr(), pk, nkeys, pa, nb, k, l, int(d), _ps(param_set), s))
+    ph, pn = _round_outputs("poly_mul_ntt_kl_round_keyed", hi, norms, nb * k, n, d)
+    _run("poly_mul_ntt_kl_round_keyed", (*ins, hi, norms), stream,
+         ph, pn, py, ahat.data_ptr(), pk, nkeys, pa, nb, k, l, int(d), _ps(param_set))
     return hi, norms
-
-
-XOF_ALGOS = {"shake128": 0, "shake256": 1}   # NTT_XOF_SHAKE128, NTT_XOF_SHAKE256
-XOF_OUT_MAX = 512          # NTT_XOF_OUT_MAX
-XOF_PATHS = {"auto": 0, "lane": 1, "wave": 2}   # NTT_XOF_PATH_AUTO, NTT_XOF_PATH_LANE, NTT_XOF_PATH_WAVE
-XOF_PATH_AUTO, XOF_PATH_LANE, XOF_PATH_WAVE = 0, 1, 2
-CHALLENGE_H_MAX = 128      # NTT_CHALLENGE_H_MAX
-SAMPLE_Y_REFILLS_MAX = 255   # NTT_SAMPLE_Y_REFILLS_MAX
-GEN_A_BLOCKS_MAX = 256       # NTT_GEN_A_BLOCKS_MAX
-GAUSS_CHUNK = 512            # NTT_GAUSS_CHUNK
-GAUSS_ROWS_MAX = 128         # NTT_GAUSS_ROWS_MAX
-GAUSS_COLS_MAX = 4           # NTT_GAUSS_COLS_MAX
 
 
 def _byte_rows(name: str, t, batch: int) -> int:
     """Row length of a uint8/int8 device tensor [batch, ...]: a multiple of 8."""
-    torch = _torch()
-    _batch(t, 1, (torch.int8, torch.uint8), "int8/uint8")   # device, dtype, contiguity
+    _byte_batch(t)   # device, dtype, contiguity
     if t.dim() < 2 or t.shape[0] != batch:
         raise ValueError(f"{name}: shape {tuple(t.shape)}, expected [{batch}, bytes]")
     row = int(np.prod(t.shape[1:]))
@@ -683,14 +525,54 @@ def _xof_path(path) -> int:
     return XOF_PATHS[path]
 
 
+def _xof_algo(algo) -> int:
+    if isinstance(algo, str) and algo not in XOF_ALGOS:
+        raise ValueError(f"algo {algo!r}, expected one of {sorted(XOF_ALGOS)}")
+    return XOF_ALGOS[algo] if isinstance(algo, str) else int(algo)
+
+
+def _xof_cstm(cstm) -> int:
+    c = -1 if cstm is None else int(cstm)
+    if cstm is not None and not 0 <= c <= 0xFFFF:
+        raise ValueError(f"cstm = {cstm}, expected None or 0 .. 65535")
+    return c
+
+
+def _seed_rows(seed, batch: int, shake256: bool = False) -> int:
+    """Bytes per seed of seed [batch, seedlen]: a multiple of 8 within 8 .. 160,
+    8 .. 128 for the samplers under SHAKE256."""
+    seedlen = _byte_rows("seed", seed, batch)
+    smax = 128 if shake256 else 160
+    if seed.dim() != 2 or not 8 <= seedlen <= smax:
+        raise ValueError(f"seed: shape {tuple(seed.shape)}, expected [{batch}, 8 .. {smax}]")
+    return seedlen
+
+
+def _nonce(nonce) -> int:
+    if not 0 <= int(nonce) <= 255:
+        raise ValueError(f"nonce = {nonce}, expected 0 .. 255")
+    return int(nonce)
+
+
+def _nonces(nonces, batch: int):
+    """The per-message nonces, None or int32 [batch]: their pointer."""
+    if nonces is not None and (_batch(nonces, 1) != batch or nonces.dim() != 1):
+        raise ValueError(f"nonces: shape {tuple(nonces.shape)}, expected [{batch}]")
+    return _ptr(nonces)
+
+
+def _pstride(pstride, n: int) -> int:
+    pstride = n if pstride is None else int(pstride)
+    if pstride < n or pstride % 4:
+        raise ValueError(f"pstride = {pstride}, expected a multiple of 4 and >= n = {n}")
+    return pstride
+
+
 def xof_small_batch_max(algo="shake256", ragged: bool = False) -> int:
     """Largest batch at which xof (ragged False) or xof_ragged (ragged True)
     with path="auto" runs the wave kernels, two messages per wave (0: never)."""
-    if isinstance(algo, str) and algo not in XOF_ALGOS:
-        raise ValueError(f"algo {algo!r}, expected one of {sorted(XOF_ALGOS)}")
-    a = XOF_ALGOS[algo] if isinstance(algo, str) else int(algo)
     v = _sz()
-    _check(lib().ntt_xof_small_batch_max(a, int(bool(ragged)), ctypes.byref(v)), "ntt_xof_small_batch_max")
+    _check(lib().ntt_xof_small_batch_max(_xof_algo(algo), int(bool(ragged)), ctypes.byref(v)), "ntt_xof_small_batch_max")
     return v.value
 
 
@@ -717,17 +599,10 @@ def xof(out, in0, in1=None, algo="shake256", cstm=None, stream=None, path="auto"
     len1 = 0 if in1 is None else _byte_rows("in1", in1, nb)
     if len0 + len1 >= 1 << 32:
         raise ValueError("message of 2^32 bytes or more")
-    if isinstance(algo, str) and algo not in XOF_ALGOS:
-        raise ValueError(f"algo {algo!r}, expected one of {sorted(XOF_ALGOS)}")
-    a = XOF_ALGOS[algo] if isinstance(algo, str) else int(algo)
-    c = -1 if cstm is None else int(cstm)
-    if cstm is not None and not 0 <= c <= 0xFFFF:
-        raise ValueError(f"cstm = {cstm}, expected None or 0 .. 65535")
+    a, c = _xof_algo(algo), _xof_cstm(cstm)
     p0 = in0.data_ptr() if len0 else None
     p1 = in1.data_ptr() if len1 else None
-    tensors = (out, in0) if in1 is None else (out, in0, in1)
-    fn = lib().ntt_xof_path
-    _run("ntt_xof", tensors, stream, lambda s: fn(out.data_ptr(), outlen, p0, len0, p1, len1, nb, a, c, pth, s))
+    _run("ntt_xof_path", (out, in0, in1), stream, out.data_ptr(), outlen, p0, len0, p1, len1, nb, a, c, pth)
     return out
 
 
@@ -747,7 +622,7 @@ def xof_ragged(out, msg, off, algo="shake256", cstm=None, stream=None, path="aut
     before the devices.  Returns out."""
     torch = _torch()
     for name, t in (("out", out), ("msg", msg)):
-        if t.dtype not in (torch.int8, torch.uint8):
+        if t.dtype not in _BYTE_DTYPES:
             raise TypeError(f"{name}: expected int8/uint8 storage, got {t.dtype}")
     if off.dtype != torch.int64:
         raise TypeError(f"off: expected int64 storage (the offsets' uint64 bits), got {off.dtype}")
@@ -767,17 +642,10 @@ def xof_ragged(out, msg, off, algo="shake256", cstm=None, stream=None, path="aut
     for name, t in (("out", out), ("msg", msg), ("off", off)):
         if not t.is_contiguous():
             raise ValueError(f"{name}: tensor must be contiguous")
-    if isinstance(algo, str) and algo not in XOF_ALGOS:
-        raise ValueError(f"algo {algo!r}, expected one of {sorted(XOF_ALGOS)}")
-    a = XOF_ALGOS[algo] if isinstance(algo, str) else int(algo)
-    c = -1 if cstm is None else int(cstm)
-    if cstm is not None and not 0 <= c <= 0xFFFF:
-        raise ValueError(f"cstm = {cstm}, expected None or 0 .. 65535")
+    a, c = _xof_algo(algo), _xof_cstm(cstm)
     pm = msg.data_ptr() if msg_bytes else None
-    pth = _xof_path(path)
-    fn = lib().ntt_xof_ragged_path
-    _run("ntt_xof_ragged", (out, msg, off), stream,
-         lambda s: fn(out.data_ptr(), outlen, pm, msg_bytes, off.data_ptr(), nb, a, c, pth, s))
+    _run("ntt_xof_ragged_path", (out, msg, off), stream,
+         out.data_ptr(), outlen, pm, msg_bytes, off.data_ptr(), nb, a, c, _xof_path(path))
     return out
 
 
@@ -806,12 +674,9 @@ def poly_challenge(pos, val, seed, param_set, stream=None):
         _batch(t, 1)   # device, dtype, contiguity
     if not 1 <= h <= CHALLENGE_H_MAX:
         raise ValueError(f"h = {h}, expected 1 .. {CHALLENGE_H_MAX}")
-    seedlen = _byte_rows("seed", seed, nb)
-    if seed.dim() != 2 or not 8 <= seedlen <= 160:
-        raise ValueError(f"seed: shape {tuple(seed.shape)}, expected [{nb}, 8 .. 160]")
-    fn = lib().poly_challenge
+    seedlen = _seed_rows(seed, nb)
     _run("poly_challenge", (pos, val, seed), stream,
-         lambda s: fn(pos.data_ptr(), val.data_ptr(), seed.data_ptr(), seedlen, nb, h, _ps(param_set), s))
+         pos.data_ptr(), val.data_ptr(), seed.data_ptr(), seedlen, nb, h, _ps(param_set))
     return pos, val
 
 
@@ -828,24 +693,10 @@ def poly_sample_y(y, seed, param_set, bits: int, algo="shake256", nonce: int = 0
         raise ValueError(f"y: shape {tuple(y.shape)}, expected [{nb}, n] or flat")
     if not 2 <= int(bits) <= 24:
         raise ValueError(f"bits = {bits}, expected 2 .. 24")
-    if not 0 <= int(nonce) <= 255:
-        raise ValueError(f"nonce = {nonce}, expected 0 .. 255")
-    if isinstance(algo, str) and algo not in XOF_ALGOS:
-        raise ValueError(f"algo {algo!r}, expected one of {sorted(XOF_ALGOS)}")
-    a = XOF_ALGOS[algo] if isinstance(algo, str) else int(algo)
-    seedlen = _byte_rows("seed", seed, nb)
-    smax = 128 if a == XOF_ALGOS["shake256"] else 160
-    if seed.dim() != 2 or not 8 <= seedlen <= smax:
-        raise ValueError(f"seed: shape {tuple(seed.shape)}, expected [{nb}, 8 .. {smax}]")
-    tensors = (y, seed)
-    pn = None
-    if nonces is not None:
-        if _batch(nonces, 1) != nb or nonces.dim() != 1:
-            raise ValueError(f"nonces: shape {tuple(nonces.shape)}, expected [{nb}]")
-        tensors, pn = (y, seed, nonces), nonces.data_ptr()
-    fn = lib().poly_sample_y
-    _run("poly_sample_y", tensors, stream,
-         lambda s: fn(y.data_ptr(), seed.data_ptr(), seedlen, pn, int(nonce), nb, int(bits), a, _ps(param_set), s))
+    nonce, a = _nonce(nonce), _xof_algo(algo)
+    seedlen = _seed_rows(seed, nb, a == XOF_ALGOS["shake256"])
+    _run("poly_sample_y", (y, seed, nonces), stream,
+         y.data_ptr(), seed.data_ptr(), seedlen, _nonces(nonces, nb), nonce, nb, int(bits), a, _ps(param_set))
     return y
 
 
@@ -866,20 +717,15 @@ def poly_gen_a(a, seed, param_set, nblocks: int, k: int, pstride=None, stream=No
         raise ValueError(f"k = {k}, expected 1 .. {MUL_K_MAX}")
     if not 1 <= int(nblocks) <= GEN_A_BLOCKS_MAX:
         raise ValueError(f"nblocks = {nblocks}, expected 1 .. {GEN_A_BLOCKS_MAX}")
-    pstride = n if pstride is None else int(pstride)
-    if pstride < n or pstride % 4:
-        raise ValueError(f"pstride = {pstride}, expected a multiple of 4 and >= n = {n}")
-    if seed.dim() != 2:
+    pstride = _pstride(pstride, n)
+    if seed.dim() != 2:   # the batch is the seeds': their shape first, worded without it
         raise ValueError(f"seed: shape {tuple(seed.shape)}, expected [batch, 8 .. 160]")
     nb = seed.shape[0]
-    seedlen = _byte_rows("seed", seed, nb)
-    if not 8 <= seedlen <= 160:
-        raise ValueError(f"seed: shape {tuple(seed.shape)}, expected [{nb}, 8 .. 160]")
+    seedlen = _seed_rows(seed, nb)
     if a.numel() != nb * int(k) * pstride:
         raise ValueError(f"a: numel {a.numel()} is not batch*k*pstride = {nb}*{k}*{pstride}")
-    fn = lib().poly_gen_a
     _run("poly_gen_a", (a, seed), stream,
-         lambda s: fn(a.data_ptr(), pstride, seed.data_ptr(), seedlen, nb, int(k), int(nblocks), _ps(param_set), s))
+         a.data_ptr(), pstride, seed.data_ptr(), seedlen, nb, int(k), int(nblocks), _ps(param_set))
     return a
 
 
@@ -900,25 +746,10 @@ def poly_sample_gauss(out, seed, cdt, param_set, algo="shake256", nonce: int = 0
     if cdt.dim() != 2 or not 1 <= cdt.shape[0] <= GAUSS_ROWS_MAX or not 1 <= cdt.shape[1] <= GAUSS_COLS_MAX:
         raise ValueError(f"cdt: shape {tuple(cdt.shape)}, expected [1 .. {GAUSS_ROWS_MAX}, 1 .. {GAUSS_COLS_MAX}]")
     rows, cols = cdt.shape
-    if not 0 <= int(nonce) <= 255:
-        raise ValueError(f"nonce = {nonce}, expected 0 .. 255")
-    if isinstance(algo, str) and algo not in XOF_ALGOS:
-        raise ValueError(f"algo {algo!r}, expected one of {sorted(XOF_ALGOS)}")
-    a = XOF_ALGOS[algo] if isinstance(algo, str) else int(algo)
-    seedlen = _byte_rows("seed", seed, nb)
-    smax = 128 if a == XOF_ALGOS["shake256"] else 160
-    if seed.dim() != 2 or not 8 <= seedlen <= smax:
-        raise ValueError(f"seed: shape {tuple(seed.shape)}, expected [{nb}, 8 .. {smax}]")
-    tensors = (out, seed, cdt)
-    pn = None
-    if nonces is not None:
-        if _batch(nonces, 1) != nb or nonces.dim() != 1:
-            raise ValueError(f"nonces: shape {tuple(nonces.shape)}, expected [{nb}]")
-        tensors, pn = (out, seed, cdt, nonces), nonces.data_ptr()
-    fn = lib().poly_sample_gauss
-    _run("poly_sample_gauss", tensors, stream,
-         lambda s: fn(out.data_ptr(), seed.data_ptr(), seedlen, pn, int(nonce), cdt.data_ptr(), rows, cols, nb, a,
-                      _ps(param_set), s))
+    nonce, a = _nonce(nonce), _xof_algo(algo)
+    seedlen = _seed_rows(seed, nb, a == XOF_ALGOS["shake256"])
+    _run("poly_sample_gauss", (out, seed, cdt, nonces), stream, out.data_ptr(), seed.data_ptr(), seedlen,
+         _nonces(nonces, nb), nonce, cdt.data_ptr(), rows, cols, nb, a, _ps(param_set))
     return out
 
 
@@ -934,8 +765,7 @@ def poly_hsum(sums, w, param_set, h: int, stream=None):
         raise ValueError(f"sums: numel {sums.numel()} is not the batch {nb}")
     if not 1 <= int(h) <= n:
         raise ValueError(f"h = {h}, expected 1 .. {n}")
-    fn = lib().poly_hsum
-    _run("poly_hsum", (sums, w), stream, lambda s: fn(sums.data_ptr(), w.data_ptr(), nb, int(h), _ps(param_set), s))
+    _run("poly_hsum", (sums, w), stream, sums.data_ptr(), w.data_ptr(), nb, int(h), _ps(param_set))
     return sums
 
 
@@ -944,31 +774,46 @@ def _pack_operands(rows, w, param_set, bits, signed, maxima=None):
     and the tensors given, for _run.  rows is int8/uint8 [batch, stride], w
     int32 [batch, k, n] or [batch, n], maxima None or int32 with batch*k
     elements."""
-    torch = _torch()
-    info = param_info(param_set)
-    n, qbits = info["n"], info["q"].bit_length()
-    _batch(rows, 1, (torch.int8, torch.uint8), "int8/uint8")   # device, dtype, contiguity
-    if rows.dim() != 2:
-        raise ValueError(f"rows: shape {tuple(rows.shape)}, expected [batch, stride]")
-    nb, stride = rows.shape
+    n, nb, stride = _packed_rows("rows", rows, param_set)
     _batch(w, n)
     if w.dim() < 2 or w.shape[0] != nb:
         raise ValueError(f"w: shape {tuple(w.shape)}, expected [{nb}, k, {n}] or [{nb}, {n}]")
     k = w.numel() // (nb * n) if nb else 1
     if w.numel() != nb * k * n or not 1 <= k <= MUL_K_MAX:
         raise ValueError(f"w: numel {w.numel()} is not batch*k*n = {nb}*k*{n} with 1 <= k <= {MUL_K_MAX}")
+    sgn = _packed_fields("rows", stride, k, bits, signed, param_set)
+    _maxima(maxima, nb, k)
+    return nb, stride, k, sgn, (rows, w, maxima)
+
+
+def _packed_rows(name: str, rows, param_set):
+    """The packed side of poly_pack / poly_unpack / poly_unpack_ntt, int8/uint8
+    [batch, stride]: n, batch and stride."""
+    n = _n(param_set)
+    _byte_batch(rows)   # device, dtype, contiguity
+    if rows.dim() != 2:
+        raise ValueError(f"{name}: shape {tuple(rows.shape)}, expected [batch, stride]")
+    return (n, *rows.shape)
+
+
+def _packed_fields(name: str, stride: int, k: int, bits, signed, param_set) -> int:
+    """The field geometry of the packed rows `name`, checked: bits against q's
+    bit length, stride against the k*n*bits/8 bytes of a row.  Returns sgn."""
+    info = param_info(param_set)
+    n, qbits = info["n"], info["q"].bit_length()
     sgn = 1 if signed else 0
     if not 8 <= int(bits) <= qbits - sgn:
         raise ValueError(f"bits = {bits}, expected 8 .. {qbits - sgn} ({'signed' if sgn else 'unsigned'})")
     packed = k * n * int(bits) // 8
     if stride % 16 or stride < packed:
-        raise ValueError(f"rows: stride {stride}, expected a multiple of 16 and >= k*n*bits/8 = {packed}")
-    tensors = (rows, w)
-    if maxima is not None:
-        if _batch(maxima, 1) != nb * k:
-            raise ValueError(f"maxima: numel {maxima.numel()} is not batch*k = {nb}*{k}")
-        tensors = (rows, w, maxima)
-    return nb, stride, k, sgn, tensors
+        raise ValueError(f"{name}: stride {stride}, expected a multiple of 16 and >= k*n*bits/8 = {packed}")
+    return sgn
+
+
+def _maxima(maxima, nb: int, k: int):
+    """poly_unpack's maxima: None or int32 with one element per polynomial."""
+    if maxima is not None and _batch(maxima, 1) != nb * k:
+        raise ValueError(f"maxima: numel {maxima.numel()} is not batch*k = {nb}*{k}")
 
 
 def poly_pack(out, w, param_set, bits: int, signed=True, stream=None):
@@ -981,9 +826,7 @@ def poly_pack(out, w, param_set, bits: int, signed=True, stream=None):
     field's range is truncated.  Bytes of a row beyond k*n*bits/8 are not
     written.  8 <= bits <= bit length of q, less one when signed.  Returns out."""
     nb, stride, k, sgn, tensors = _pack_operands(out, w, param_set, bits, signed)
-    fn = lib().poly_pack
-    _run("poly_pack", tensors, stream,
-         lambda s: fn(out.data_ptr(), stride, w.data_ptr(), nb, k, int(bits), sgn, _ps(param_set), s))
+    _run("poly_pack", tensors, stream, out.data_ptr(), stride, w.data_ptr(), nb, k, int(bits), sgn, _ps(param_set))
     return out
 
 
@@ -995,10 +838,8 @@ def poly_unpack(w, inp, param_set, bits: int, signed=True, maxima=None, stream=N
     maximum >= q is a malformed key).  Bytes of a row beyond k*n*bits/8 are not
     read.  Returns (w, maxima)."""
     nb, stride, k, sgn, tensors = _pack_operands(inp, w, param_set, bits, signed, maxima)
-    fn = lib().poly_unpack
-    pm = None if maxima is None else maxima.data_ptr()
     _run("poly_unpack", tensors, stream,
-         lambda s: fn(w.data_ptr(), pm, inp.data_ptr(), stride, nb, k, int(bits), sgn, _ps(param_set), s))
+         w.data_ptr(), _ptr(maxima), inp.data_ptr(), stride, nb, k, int(bits), sgn, _ps(param_set))
     return w, maxima
 
 
@@ -1017,42 +858,20 @@ def poly_unpack_ntt(out, inp, param_set, bits: int, k: int, signed=False, negate
     (negate=True: q - t-hat).  maxima is poly_unpack's: None or int32 with
     batch*k elements.  Parameter sets "ref", "p-I", "p-III".  Returns
     (out, maxima)."""
-    torch = _torch()
-    info = param_info(param_set)
-    n, qbits = info["n"], info["q"].bit_length()
-    _batch(inp, 1, (torch.int8, torch.uint8), "int8/uint8")   # device, dtype, contiguity
-    if inp.dim() != 2:
-        raise ValueError(f"inp: shape {tuple(inp.shape)}, expected [batch, stride]")
-    nb, stride = inp.shape
+    n, nb, stride = _packed_rows("inp", inp, param_set)
     _batch(out, 1)
     if not 1 <= int(k) <= MUL_K_MAX:
         raise ValueError(f"k = {k}, expected 1 .. {MUL_K_MAX}")
     k = int(k)
-    sgn = 1 if signed else 0
-    if not 8 <= int(bits) <= qbits - sgn:
-        raise ValueError(f"bits = {bits}, expected 8 .. {qbits - sgn} ({'signed' if sgn else 'unsigned'})")
-    packed = k * n * int(bits) // 8
-    if stride % 16 or stride < packed:
-        raise ValueError(f"inp: stride {stride}, expected a multiple of 16 and >= k*n*bits/8 = {packed}")
-    pstride = n if pstride is None else int(pstride)
-    if pstride < n or pstride % 4:
-        raise ValueError(f"pstride = {pstride}, expected a multiple of 4 and >= n = {n}")
+    sgn = _packed_fields("inp", stride, k, bits, signed, param_set)
+    pstride = _pstride(pstride, n)
     if nb and out.numel() not in (nb * k * pstride, (nb * k - 1) * pstride + n):
         raise ValueError(f"out: numel {out.numel()} is neither batch*k*pstride = {nb}*{k}*{pstride} "
                          f"nor (batch*k - 1)*pstride + n")
-    tensors, pm = (out, inp), None
-    if maxima is not None:
-        if _batch(maxima, 1) != nb * k:
-            raise ValueError(f"maxima: numel {maxima.numel()} is not batch*k = {nb}*{k}")
-        tensors, pm = (out, inp, maxima), maxima.data_ptr()
-    fn = lib().poly_unpack_ntt
-    _run("poly_unpack_ntt", tensors, stream,
-         lambda s: fn(out.data_ptr(), pstride, pm, inp.data_ptr(), stride, nb, k, int(bits), sgn, 1 if negate else 0,
-                      _ps(param_set), s))
+    _maxima(maxima, nb, k)
+    _run("poly_unpack_ntt", (out, inp, maxima), stream, out.data_ptr(), pstride, _ptr(maxima), inp.data_ptr(), stride,
+         nb, k, int(bits), sgn, 1 if negate else 0, _ps(param_set))
     return out, maxima
-
-
-ROWS_M_MAX = 16   # NTT_ROWS_M_MAX
 
 
 def _words(name: str, t, numel=None):
@@ -1116,9 +935,8 @@ def rows_over(flag, vals, bounds, accumulate=False, stream=None):
     if any(not 0 <= x < 1 << 64 for x in bounds):
         raise ValueError("bounds: expected 0 .. 2^64 - 1")
     arr = (ctypes.c_uint64 * m)(*bounds)
-    fn = lib().ntt_rows_over
     _run("ntt_rows_over", (flag, vals), stream,
-         lambda s: fn(flag.data_ptr(), vals.data_ptr(), width, m, arr, 1 if accumulate else 0, nb, s))
+         flag.data_ptr(), vals.data_ptr(), width, m, arr, 1 if accumulate else 0, nb)
     return flag
 
 
@@ -1133,9 +951,8 @@ def rows_differ(flag, a, b, accumulate=False, stream=None):
     if na != nb or row_bytes != row_b:
         raise ValueError(f"a / b: {na} rows of {row_bytes} bytes and {nb} rows of {row_b} bytes")
     _words("flag", flag, nb)
-    fn = lib().ntt_rows_differ
     _run("ntt_rows_differ", (flag, a, b), stream,
-         lambda s: fn(flag.data_ptr(), a.data_ptr(), sa, b.data_ptr(), sb, row_bytes, 1 if accumulate else 0, nb, s))
+         flag.data_ptr(), a.data_ptr(), sa, b.data_ptr(), sb, row_bytes, 1 if accumulate else 0, nb)
     return flag
 
 
@@ -1150,11 +967,10 @@ def select(idx, count, flag, want, bump=None, stream=None):
     _words("count", count, 1)
     if want not in (0, 1, False, True):
         raise ValueError(f"want = {want!r}, expected False / True")
-    tensors, pb = (idx, count, flag), None
     if bump is not None:
-        tensors, pb = (idx, count, flag, _words("bump", bump, nb)), bump.data_ptr()
-    fn = lib().ntt_select
-    _run("ntt_select", tensors, stream, lambda s: fn(idx.data_ptr(), count.data_ptr(), flag.data_ptr(), int(want), pb, nb, s))
+        _words("bump", bump, nb)
+    _run("ntt_select", (idx, count, flag, bump), stream,
+         idx.data_ptr(), count.data_ptr(), flag.data_ptr(), int(want), _ptr(bump), nb)
     return idx, count
 
 
@@ -1180,11 +996,8 @@ def rows_move(dst, src, dst_idx=None, src_idx=None, count=None, n=None, stream=N
         raise ValueError(f"n = {n} with index lists of {[t.numel() for _, t in lists]} entries")
     if count is not None:
         _words("count", count, 1)
-    tensors = (dst, src) + tuple(t for _, t in lists) + (() if count is None else (count,))
-    pd, psrc, pc = (None if t is None else t.data_ptr() for t in (dst_idx, src_idx, count))
-    fn = lib().ntt_rows_move
-    _run("ntt_rows_move", tensors, stream,
-         lambda s: fn(dst.data_ptr(), ds, pd, dr, src.data_ptr(), ss, psrc, sr, row_bytes, pc, n, s))
+    _run("ntt_rows_move", (dst, src, dst_idx, src_idx, count), stream, dst.data_ptr(), ds, _ptr(dst_idx), dr,
+         src.data_ptr(), ss, _ptr(src_idx), sr, row_bytes, _ptr(count), n)
     return dst
 
 
@@ -1205,8 +1018,7 @@ def fill_uniform(t, param_set, seed: int, first_poly: int = 0, stream=None):
     """Device-side counter-based uniform coefficients in [0, q)."""
     n = _n(param_set)
     b = _batch(t, n)
-    _run("ntt_fill_uniform", (t,), stream,
-         lambda s: lib().ntt_fill_uniform(t.data_ptr(), b, _ps(param_set), seed & (2**64 - 1), first_poly, s))
+    _run("ntt_fill_uniform", (t,), stream, t.data_ptr(), b, _ps(param_set), seed & (2**64 - 1), first_poly)
     return t
 
 
@@ -1259,19 +1071,18 @@ class HostContext:
             raise ValueError(f"{name}: size {x.size} is not a multiple of n={self.n}")
         return x.size // self.n
 
-    def ntt(self, out, inp):
+    def _oop(self, name, out, inp):
         b = self._arr(inp, "inp")
         if self._arr(out, "out") != b:
             raise ValueError("out/in batch mismatch")
-        _check(lib().poly_ntt_host(self._h, out.ctypes.data, inp.ctypes.data, b), "poly_ntt_host")
+        _check(_FN[name](self._h, out.ctypes.data, inp.ctypes.data, b), name)
         return out
 
+    def ntt(self, out, inp):
+        return self._oop("poly_ntt_host", out, inp)
+
     def invntt(self, out, inp):
-        b = self._arr(inp, "inp")
-        if self._arr(out, "out") != b:
-            raise ValueError("out/in batch mismatch")
-        _check(lib().poly_invntt_host(self._h, out.ctypes.data, inp.ctypes.data, b), "poly_invntt_host")
-        return out
+        return self._oop("poly_invntt_host", out, inp)
 
     def mul(self, c, a, b):
         nb = self._arr(a, "a")
